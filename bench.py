@@ -31,7 +31,10 @@ RCCL gather of the packed blocks to rank 0 over xGMI every --flush steps (issued
 priorities), then rank 0's copy stream drains each gathered slot to pinned host memory.  The rate with the ring kept in
 rank 0's HBM is measured right after and reported beside it (`hbm_ring`); `ranks[]` carries every rank's own roofline.
 
-Prints ONE JSON line on rank 0 (contract in the task statement).  Every leg -- the headline, `configs4_shard_on_one_gpu`,
+Prints ONE JSON line on rank 0 (contract in the task statement), under 8 KiB: the full record, with every side leg's probe
+report, goes to stderr as `[bench] full record: {...}` and the line keeps of a side leg its rate, `frac`, `timed_over_probe`
+and `stack_verified` (result_line).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
+Every leg -- the headline, `configs4_shard_on_one_gpu`,
 `bf16_stack`, `configs3_on_one_gpu.{one_shot,chunks_4}` -- carries `stack_buffer_probe`, `stack_verified` (the timed buffer
 holds the right bytes; a failure voids the line) and its own `roofline` (HIP events on the write's stream around every
 --event-every-th write; `probe_ms_chosen`, `timed_write_ms`, `timed_over_probe`, `default_buffer`, `workgroup_shares` = the XCD bias in force and the probe's biased-against-equal timing); `cpu_baseline` (the
@@ -127,6 +130,10 @@ def parse(argv=None):
     ap.add_argument("--nn-dtype", default="f32", choices=["f32", "bf16"],
                     help="dtype of the NN_11 forward: f32 as upstream (default; ~18 TFLOP/s in stock MIOpen = 23 s per "
                          "step at 65 536 lattices) or bf16 autocast")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MiB; rank 0).  The lattices are first brought to a step count fixed by the arguments, so "
+                         "that the same arguments time the same inputs in every run (default path only)")
     return ap.parse_args(argv)
 
 
@@ -394,6 +401,17 @@ class ExploreLeg:
         torch.cuda.synchronize(self.device)
         return out
 
+    def align(self, target):
+        """Untimed passes of the loop up to pass `target`: the lattices evolve by loop passes alone, and the probe, a re-probe
+        and the quiet check take as many passes as the timing asks for -- after this the timed region starts from lattices
+        fixed by the arguments (--dump-outputs)."""
+        if self.loop.t > target or target % self.flush:
+            sys.exit("bench.py: set-up took %d loop passes; the timed region cannot start at pass %d" % (self.loop.t, target))
+        while self.loop.t < target:
+            self.loop.step()
+        self.loop.drain()
+        self.torch.cuda.synchronize(self.device)
+
     def prepare(self, K, every):
         """Create the timed region's events BEFORE it starts (torch creates the HIP event at the first record: that call
         belongs to set-up, not between two launches of the timed region)."""
@@ -518,6 +536,121 @@ def time_explore_leg(T, torch, env, n, d, seed, tdtype, flush, device, steps, wa
     return out
 
 
+def setup_passes_bound(candidates, W, flush):
+    """Most loop passes ExploreLeg's set-up (pick_stack + warm) can take, rounded up to a block boundary: the probe times
+    every candidate in 2 x 6 passes, up to twice the candidates asked for when it extends its search, then the shares
+    check (24) and SETTLE + 9; the warm-up W, a re-probe of all of them again (+ 24 + 5), the quiet check (40 flush
+    windows at most) and the alignment to a block (< flush)."""
+    c = max(1, candidates)
+    b = 24 * c + 24 + SETTLE + 9 + max(W, 1) + 24 * c + 24 + 5 + 41 * flush
+    return b + (-b) % flush
+
+
+DUMP_BUDGET = 64 << 20      # bytes --dump-outputs may write in all
+
+
+def dump_outputs(leg, out_dir, seed):
+    """--dump-outputs: what the LAST timed step handed its caller, as .npy files in out_dir (the stack and the syndrome planes
+    float32, the integers float64): the perspective stack the step wrote (`stack`) with its `positions` -- a fixed
+    sample of rows drawn with `seed` when there are more than 24 MiB of them, their row numbers in `stack_rows` -- the
+    scan (`offsets`, N + 1), and for a fixed sample of lattices (`lattices`) the transition the step recorded
+    (`transition_*`; `transition_priority` when the step closed a block) and the syndrome it left (`states`).  Must run
+    before verify(), which rewrites the stack buffer.  -> {file name: bytes}."""
+    torch, n, nq = leg.torch, leg.n, leg.nq
+    leg.loop.drain()
+    torch.cuda.synchronize(leg.device)
+    t = leg.loop.t - 1
+    off = leg.offs[t % leg.offs.shape[0]][:n + 1]
+    lo = (leg.chunks - 1) * (n // leg.chunks)                   # the buffer holds the last range of lattices of the step
+    P = int((off[n] - off[lo]).item())
+    rng = np.random.default_rng(seed)
+
+    def sample(total, item_bytes, budget):
+        k = min(total, budget // item_bytes)
+        return np.arange(total) if k == total else np.sort(rng.choice(total, k, replace=False))
+
+    def dev(idx):
+        return torch.as_tensor(idx, dtype=torch.int64, device=leg.device)
+
+    out = {}
+    rows = sample(P, nq * 4 + 4 * 8, 24 << 20)                  # stack + positions + row number
+    out["stack"] = leg.stack[:P][dev(rows)].float()
+    out["positions"] = leg.positions[:P][dev(rows)].double()
+    out["stack_rows"] = rows.astype(np.float64)
+    oi = sample(n + 1, 8, 8 << 20)
+    out["offsets"] = off[dev(oi)].double()
+    if oi.size <= n:
+        out["offsets_index"] = oi.astype(np.float64)
+    per_lattice = 3 * nq * 4 + 4 * 8 + 4 * 8                    # 3 planes, action, reward / terminal / priority / lattice number
+    lat = sample(n, per_lattice, 24 << 20)
+    out["lattices"] = lat.astype(np.float64)
+    li = dev(lat)
+    if leg.blocks is not None:
+        blk = leg.blocks[(t // leg.flush) % len(leg.blocks)]
+        u = blk.unpack(first=(t % leg.flush) * n, count=n)
+        out["transition_perspective"] = u["perspective"][li].float()
+        out["transition_next_perspective"] = u["next_perspective"][li].float()
+        out["transition_action"] = u["action"][li].double()
+        out["transition_reward"] = u["reward"][li].double()
+        out["transition_terminal"] = u["terminal"][li].double()
+        if (t + 1) % leg.flush == 0:
+            out["transition_priority"] = u["priority"][li].double()
+    out["states"] = leg.envs.getStates()[li].float()
+    os.makedirs(out_dir, exist_ok=True)
+    sizes = {}
+    for name, a in out.items():
+        a = a.cpu().numpy() if leg.torch.is_tensor(a) else a
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a)
+        sizes[name + ".npy"] = os.path.getsize(path)
+    assert sum(sizes.values()) <= DUMP_BUDGET, sizes
+    return sizes
+
+
+# what the result line leaves out of the full record: probe addresses and per-sample minima, prose, and of every side leg
+# all but its rate, its write's fraction of the HBM peak and its check against the probe (tools that read the line keep
+# only the last few KB of stdout)
+LINE_DROPS = ("addresses", "write_ms_min", "note", "how", "sample", "timed_launches", "traffic_source")
+SIDE_LEGS = ("configs4_shard_on_one_gpu", "bf16_stack")
+LINE_LIMIT = 8192
+
+
+def _leg_brief(leg):
+    roof = leg.get("roofline") or {}
+    return {"value": leg["value"], "ms_per_step": leg["ms_per_step"], "perspectives_per_sec": leg["perspectives_per_sec"],
+            "frac": roof.get("frac"), "timed_over_probe": roof.get("timed_over_probe"), "stack_verified": leg["stack_verified"]["ok"]}
+
+
+def _drop_detail(x):
+    if isinstance(x, dict):
+        return {k: _drop_detail(v) for k, v in x.items() if k not in LINE_DROPS}
+    if isinstance(x, list):
+        return [_drop_detail(v) for v in x]
+    return x
+
+
+def result_line(res):
+    """The one JSON line on stdout: the record without LINE_DROPS, every side leg as _leg_brief."""
+    line = dict(res)
+    for k in SIDE_LEGS:
+        if k in line:
+            line[k] = _leg_brief(line[k])
+    if "configs3_on_one_gpu" in line:
+        c3 = line["configs3_on_one_gpu"]
+        line["configs3_on_one_gpu"] = dict({k: v for k, v in c3.items() if not isinstance(v, dict)},
+                                           **{k: _leg_brief(v) for k, v in c3.items() if isinstance(v, dict)})
+    return json.dumps(_drop_detail(line))
+
+
+def print_result(res, result_out):
+    """The full record on stderr (one line), the result line on stdout."""
+    print("[bench] full record: " + json.dumps(res), file=sys.stderr, flush=True)
+    line = result_line(res)
+    if len(line) >= LINE_LIMIT:
+        print("[bench] the result line has %d bytes, more than %d" % (len(line), LINE_LIMIT), file=sys.stderr, flush=True)
+    print(line, file=result_out, flush=True)
+
+
 def load_trained_weights(d):
     """The reference's trained NN_11 state_dict for size d, committed as a data fixture (tests/golden/nn11_d*.safetensors,
     made by tests/golden/make_weights.py from network/converged/*.pt with weights_only=True), or None."""
@@ -626,6 +759,8 @@ def main():
     ctx = types.SimpleNamespace(args=args, world=world, rank=rank, device=device, red_dev=red_dev, dist_on=dist_on, backend=backend,
                                 result_out=result_out)
     if max(1, args.shards) > 1 or args.graph or args.policy == "nn11":
+        if args.dump_outputs:
+            sys.exit("--dump-outputs: the default path only (not --shards > 1, --graph or --policy nn11)")
         return run_serial(ctx)
     return run_explore(ctx)
 
@@ -693,12 +828,15 @@ def run_explore(ctx):
     leg.pick_stack(args.stack_candidates, kinds)                 # set-up, untimed; every rank probes its own GPU
     barrier()
 
-    def timed_region():
+    def timed_region(align_to=None):
         """W untimed + K timed steps, bracketed by barrier + synchronize; -> (seconds, max over ranks; warm-up report)."""
         # the warm-up (and a rank's own re-probe) takes a rank-dependent number of passes: no collective in it -- every
         # rank issues exactly the gathers of the K timed steps, K // flush of them, at the same steps
         gather_, state["tg"] = state["tg"], None
         w = leg.warm(W, reprobe=not args.no_events)
+        if align_to is not None:
+            leg.align(align_to)
+            w["timed_region_starts_at_pass"] = align_to
         leg.prepare(K, EV)
         state["tg"] = gather_
         gc.disable()                    # no collection (and no free of device memory) inside the timed region
@@ -716,8 +854,9 @@ def run_explore(ctx):
         return float(el.item()), w
 
     state["tg"] = tg
-    elapsed, warm_report = timed_region()
+    elapsed, warm_report = timed_region(setup_passes_bound(args.stack_candidates, W, flush) if args.dump_outputs else None)
     leg.envs.check()                                              # capacity / action / reset / offsets latch
+    dumped = dump_outputs(leg, args.dump_outputs, args.seed) if args.dump_outputs and rank == 0 else None
     p_all, p_mean = leg.perspectives()
     p_sum = p_all.sum().reshape(1).to(red_dev)
     if dist_on:
@@ -932,7 +1071,9 @@ def run_explore(ctx):
             res["nn_in_loop"] = nn_leg
         if world == 1 and args.cpu_seconds > 0:
             res["cpu_baseline"] = cpu_baseline(d, args.p_error, args.seed, args.cpu_seconds)
-        print(json.dumps(res), file=result_out, flush=True)
+        if dumped is not None:
+            res["dumped_outputs"] = {"dir": args.dump_outputs, "files": len(dumped), "bytes": sum(dumped.values())}
+        print_result(res, result_out)
         if void:
             print("[bench] THE TIMED STACK BUFFER HOLDS WRONG BYTES (%d): the numbers of this run are void" % verified["wrong_bytes"], file=sys.stderr, flush=True)
     leg.close()
@@ -1261,7 +1402,7 @@ def run_serial(ctx):
             res["nn_in_loop"] = nn_leg
         if world == 1 and args.cpu_seconds > 0:
             res["cpu_baseline"] = cpu_baseline(d, args.p_error, args.seed, args.cpu_seconds)
-        print(json.dumps(res), file=result_out, flush=True)
+        print_result(res, result_out)
     for sh in shards:
         sh.envs.close()
     if dist_on:

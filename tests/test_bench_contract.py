@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,6 +36,27 @@ def test_roofline_arithmetic_and_config_names():
     assert bench.config_name(1, 65536, 7, 0.10) == "configs[2]" and bench.config_name(1, 65536, 9, 0.15) == "configs[3]"
     assert bench.config_name(8, 131072, 7, 0.10) == "configs[4] shape" and bench.config_name(1, 8192, 7, 0.10) == "custom"
     assert bench.config_name(1, 4096, 5, 0.10) == "configs[1]"
+
+
+def test_result_line_of_a_full_n1_record_stays_short():
+    """The driver's command form records a line of ~30 KB with every side leg's probe in full (profiles/, round 4); the
+    result line keeps the contract's keys, and of every side leg its rate and checks, in under 8 KiB."""
+    sys.path.insert(0, ROOT)
+    import bench
+    full = json.loads(open(os.path.join(ROOT, "profiles", "r04_bench_n1_driver_form_h.json")).read().strip().splitlines()[-1])
+    line = bench.result_line(full)
+    assert len(json.dumps(full)) > 3 * bench.LINE_LIMIT and len(line) < bench.LINE_LIMIT
+    j = json.loads(line)
+    assert KEYS <= set(j) and "\n" not in line
+    for k in ("value", "ms_per_step", "steps", "warmup", "perspectives_per_lattice"):
+        assert j[k] == full[k]
+    assert j["roofline"]["frac"] == full["roofline"]["frac"] and j["stack_buffer_probe"]["kinds"][0] == "torch.empty"
+    legs = [j["configs4_shard_on_one_gpu"], j["bf16_stack"], j["configs3_on_one_gpu"]["one_shot"], j["configs3_on_one_gpu"]["chunks_4"]]
+    fulls = [full["configs4_shard_on_one_gpu"], full["bf16_stack"], full["configs3_on_one_gpu"]["one_shot"], full["configs3_on_one_gpu"]["chunks_4"]]
+    for b, f in zip(legs, fulls):
+        assert b == {"value": f["value"], "ms_per_step": f["ms_per_step"], "perspectives_per_sec": f["perspectives_per_sec"],
+                     "frac": f["roofline"]["frac"], "timed_over_probe": f["roofline"]["timed_over_probe"],
+                     "stack_verified": f["stack_verified"]["ok"]}
 
 
 def test_self_launcher_starts_the_ranks_and_relays_one_line():
@@ -112,9 +134,11 @@ def test_bench_json_contract():
                         "--cpu-seconds", "0.5", "--nn-steps", "1"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
-    assert len(lines) == 1
+    assert len(lines) == 1 and len(lines[0]) < 8192
     j = json.loads(lines[0])
     assert KEYS <= set(j)
+    full = json.loads([ln for ln in p.stderr.splitlines() if ln.startswith("[bench] full record: ")][-1].split(": ", 1)[1])
+    assert full["ms_per_step"] == j["ms_per_step"] and len(full["stack_buffer_probe"]["addresses"]) == full["stack_buffer_probe"]["candidates"]
     assert j["n_gpus"] == 1 and j["steps"] == 6 and j["warmup"] == 2 and j["higher_is_better"] is True
     assert j["scaling"] == "weak" and j["vs_baseline"] is None and j["data"] == "synthetic"
     assert "workload" in j["config"] and "model" not in j["config"]
@@ -158,3 +182,32 @@ def test_bench_graph_mode():
     j = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
     assert j["config"]["hip_graph"] is True and "roofline" not in j
     assert j["steps"] == 32 and j["value"] > 1e6 and j["perspectives_per_sec"] > 30 * j["value"]
+
+
+@pytest.mark.gpu
+def test_dump_outputs_are_the_same_in_every_run(tmp_path):
+    """--dump-outputs: two runs with the same arguments time the same inputs and write the same outputs of the last timed
+    step, float32 / float64 only, within 64 MiB; --steps is the number of timed steps."""
+    args = ["--steps", "16", "--warmup", "3", "--envs", "8192", "--cpu-seconds", "0", "--nn-steps", "0", "--stack-candidates", "3"]
+    runs = []
+    for name in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(tmp_path / name)],
+                           capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        j = json.loads([ln for ln in p.stdout.splitlines() if ln.strip()][-1])
+        assert j["steps"] == 16 and j["ms_per_step"] > 0 and j["stack_verified"]["ok"] is True
+        assert j["dumped_outputs"]["files"] == len(os.listdir(tmp_path / name)) and j["dumped_outputs"]["bytes"] <= 64 << 20
+        runs.append(j)
+    a = {f: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    b = {f: np.load(tmp_path / "b" / f) for f in sorted(os.listdir(tmp_path / "b"))}
+    assert set(a) == set(b) and {"stack.npy", "positions.npy", "offsets.npy", "states.npy", "transition_reward.npy",
+                                      "transition_priority.npy"} <= set(a)       # 16 steps from a block boundary: the last one closes a block
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and a[f].shape == b[f].shape and np.array_equal(a[f], b[f]), f
+    assert runs[0]["warm_up"]["timed_region_starts_at_pass"] == runs[1]["warm_up"]["timed_region_starts_at_pass"]
+    # the scan of the last step and the sample of its stack belong together
+    off = a["offsets.npy"]
+    assert off.shape == (8192 + 1,) and off[0] == 0 and np.all(np.diff(off) >= 0)
+    rows = a["stack_rows.npy"]
+    assert a["stack.npy"].shape == (rows.size, 2, 7, 7) and rows.max() < off[-1] and a["positions.npy"].shape == (rows.size, 3)
+    assert set(np.unique(a["stack.npy"])) <= {0.0, 1.0}
