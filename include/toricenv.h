@@ -283,6 +283,57 @@ int tq_actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float
  * lattices' counts). */
 int tq_check(tq_env* h, void* stream);
 
+/* ---- Prioritized replay memory on the device (PrioritizedReplayMemory / SumTree, src/ReplayMemory.py:45-152,
+ * src/SumTree.py).  Records are kept in the wire format above (a packed SoA ring with the block's sections minus the
+ * priority section); the priorities live in an f64 sum tree of the reference's shape: L = ceil(log2(capacity+1)) + 1
+ * levels (computed as math.log(capacity+1, 2) is), heap order, leaf i = record i.  Between calls every internal node
+ * is fl(left + right) -- the tree is a function of its leaves (no floating atomics).  Design: DESIGN.md §3.5.
+ *  - one handle, one stream: the calls of a handle share its scratch and device state; issue them on one stream, or
+ *    separate them by a synchronisation.  Capture of these calls into a HIP graph is not supported.
+ *  - set-up calls (create, destroy) allocate and synchronise; so does the first tq_replay_save_block of a block larger
+ *    than any before (its compaction scratch grows).  tq_replay_filled, tq_replay_check synchronise `stream`;
+ *    everything else only enqueues kernels.
+ *  - indices are int64 record indices (leaf numbers); uniforms / priorities / weights / tree values are f64.
+ *  - errors seen on the device are latched and reported by tq_replay_check: TQ_E_CAPACITY (a sample of more records
+ *    than are filled), TQ_E_INDEX (an index outside [0, filled), or a draw that ended on an unfilled leaf).  Nothing
+ *    outside the filled records is ever read. */
+typedef struct tq_replay tq_replay;
+
+/* PrioritizedReplayMemory(memory_size = capacity, alpha) for records of lattice size d; capacity 1..2^26, alpha >= 0.
+ * seed keys the handle's own uniforms (RNG domain 5).  faithful = 1 keeps the reference's two exponent
+ * quirks (sample's revert and reset_alpha), 0 drops them. */
+int tq_replay_create(tq_replay** out, int d, int64_t capacity, double alpha, int device, uint64_t seed, int faithful);
+int tq_replay_destroy(tq_replay* r);
+/* replay_memory.save(t, p) for every transition of a packed block of `cap` slots (IO_mp.py:60-66): the non-empty slots
+ * (action word != 0) in slot order, record k to ring position (cursor + k) % capacity; leaf = pow((double)priority,
+ * alpha); of a block with more records than the capacity only the last `capacity` survive.  block: 8-byte aligned. */
+int tq_replay_save_block(tq_replay* r, const void* block, int64_t cap, void* stream);
+/* tree.filled_size(): number of records held (synchronises `stream`); < 0 on error. */
+int64_t tq_replay_filled(tq_replay* r, void* stream);
+/* PrioritizedReplayMemory.sample(batch, beta) (ReplayMemory.py:85-124), batch 1..4096: indices, priorities (the picked
+ * leaf values) and normalised weights f64[batch] (required), and the picked records through the outputs of
+ * tq_replay_get (any may be NULL).  uniforms: device f64[batch] in [0,1), or NULL = the handle's Philox stream.  With
+ * faithful = 1 every picked leaf is then set to pow(leaf, alpha), last pick wins (the reference's "revert").  Weights
+ * that are all 0 come back as 0 (the reference raises ZeroDivisionError there). */
+int tq_replay_sample(tq_replay* r, int batch, double beta, const double* uniforms, int64_t* indices, double* priorities,
+                     double* weights, float* state, float* next_state, int64_t* actions_idx, float* rewards,
+                     uint8_t* terminals, int32_t* actions, void* stream);
+/* records at indices[0..n) -> dataToBatch's tensors (util_learner.py:7-46): state / next_state f32[n,2,d,d],
+ * actions_idx i64[n] (op - 1), rewards f32[n], terminals u8[n] (0/1), and the raw actions i32[n,4]. */
+int tq_replay_get(tq_replay* r, const int64_t* indices, int n, float* state, float* next_state, int64_t* actions_idx,
+                  float* rewards, uint8_t* terminals, int32_t* actions, void* stream);
+/* priority_update(indices, priorities) (ReplayMemory.py:126-133): leaf = pow(p, alpha); of an index listed twice the
+ * last occurrence wins. */
+int tq_replay_update(tq_replay* r, const int64_t* indices, const double* priorities, int n, void* stream);
+/* reset_alpha(alpha) (ReplayMemory.py:135-145) over the filled leaves; a zero leaf stays 0. */
+int tq_replay_reset_alpha(tq_replay* r, double alpha, void* stream);
+/* read-backs for tests: the leaves f64[capacity], the whole tree f64[tq_replay_tree_nodes(r)] (device buffers). */
+int tq_replay_leaves(tq_replay* r, double* out, void* stream);
+int64_t tq_replay_tree_nodes(const tq_replay* r);
+int tq_replay_tree(tq_replay* r, double* out, void* stream);
+/* Reads and clears the handle's device error latch (synchronises `stream`). */
+int tq_replay_check(tq_replay* r, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,5 +16,7 @@ from .policy import (NN_11, evaluate, predictMaxOptimized, seed_select, segment_
 
 from .actor import ExploreLoop, computePrioritiesParallel, run_actor  # noqa: F401,E402
 
-__all__ = ["ExploreLoop", "computePrioritiesParallel", "run_actor", "NN_11", "evaluate", "predictMaxOptimized", "segment_max", "selectActionBatch", "selectActionEnvSet", "seed_select", "prediction_smart", "generateNPlusQRandomErrors", "EnvSet", "ToricEnv", "TransitionBlock", "alloc_stack", "alloc_chunked", "generatePerspectiveBatch", "generateTransitionParallel", "make", "to_structured",
+from .replay import PrioritizedReplayMemory  # noqa: F401,E402
+
+__all__ = ["PrioritizedReplayMemory", "ExploreLoop", "computePrioritiesParallel", "run_actor", "NN_11", "evaluate", "predictMaxOptimized", "segment_max", "selectActionBatch", "selectActionEnvSet", "seed_select", "prediction_smart", "generateNPlusQRandomErrors", "EnvSet", "ToricEnv", "TransitionBlock", "alloc_stack", "alloc_chunked", "generatePerspectiveBatch", "generateTransitionParallel", "make", "to_structured",
            "transition_dtype", "ToricEnvError", "build", "load", "LIB_PATH", "SUPPORTED_SIZES"]

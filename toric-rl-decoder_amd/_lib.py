@@ -60,6 +60,18 @@ SYMBOLS = [
     ("tq_block_priorities", _i, [_i, _vp, _i64, _i, _i, _vp, _d, _vp]),
     ("tq_actor_step", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _vp]),
     ("tq_check", _i, [_vp, _vp]),
+    ("tq_replay_create", _i, [C.POINTER(_vp), _i, _i64, _d, _i, _u64, _i]),
+    ("tq_replay_destroy", _i, [_vp]),
+    ("tq_replay_save_block", _i, [_vp, _vp, _i64, _vp]),
+    ("tq_replay_filled", _i64, [_vp, _vp]),
+    ("tq_replay_sample", _i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tq_replay_get", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tq_replay_update", _i, [_vp, _vp, _vp, _i, _vp]),
+    ("tq_replay_reset_alpha", _i, [_vp, _d, _vp]),
+    ("tq_replay_leaves", _i, [_vp, _vp, _vp]),
+    ("tq_replay_tree_nodes", _i64, [_vp]),
+    ("tq_replay_tree", _i, [_vp, _vp, _vp]),
+    ("tq_replay_check", _i, [_vp, _vp]),
 ]
 
 _lib = None
@@ -71,7 +83,7 @@ class ToricEnvError(RuntimeError):
 
 def build(force=False, verbose=False):
     """Compile libtoricenv.so for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("toricenv.hip", "kernels.hpp", "stream_write.hpp", "lattice.hpp", "Makefile")]
+    srcs = [os.path.join(CSRC, f) for f in ("toricenv.hip", "kernels.hpp", "stream_write.hpp", "lattice.hpp", "replay.hpp", "Makefile")]
     srcs.append(os.path.join(_HERE, "..", "include", "toricenv.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:

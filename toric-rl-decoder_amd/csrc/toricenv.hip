@@ -16,6 +16,7 @@
 
 #include "kernels.hpp"
 #include "stream_write.hpp"
+#include "replay.hpp"
 
 namespace {
 
@@ -939,6 +940,234 @@ int tq_check(tq_env* h, void* stream_) {
     HIPCHECK(hipStreamSynchronize(stream));
     if (flag) HIPCHECK(hipMemsetAsync(h->err, 0, sizeof(int), stream));
     return decode_latch(flag);
+}
+
+}  // extern "C"
+
+// ---- prioritized replay memory (replay.hpp; contract in include/toricenv.h)
+struct tq_replay {
+    int d, w, device, faithful, L, clg;
+    int64_t cap, nchunks;                  // nchunks: rebuild chunks of 2^clg leaves that hold ring positions
+    double alpha;
+    uint64_t seed, calls, serial;          // calls: samples that drew from the handle's stream; serial: update calls
+    double* tree;                          // f64[2^L - 1]
+    void* ring;                            // tq::ring_bytes(w, cap)
+    tq::ReplayDev* st;
+    unsigned long long* stamp;             // u64[cap], last-wins stamps of the scatter update
+    int32_t* flags; int64_t* partial; int64_t* offsets; int64_t scratch_cap;   // compaction scratch of save_block
+};
+
+namespace {
+int replay_levels(int64_t cap) {        // SumTree.tree_level: math.ceil(math.log(max_size+1, 2))+1
+    return (int)ceil(log((double)cap + 1.0) / log(2.0)) + 1;
+}
+int replay_latch(int flag) {
+    if (flag & tq::RP_ERR_UNDERFILLED) return fail(TQ_E_CAPACITY, "replay sample: fewer records filled than the batch size");
+    if (flag & tq::RP_ERR_LEAF) return fail(TQ_E_INDEX, "replay sample: a draw ended on a leaf that holds no record");
+    if (flag & tq::RP_ERR_INDEX) return fail(TQ_E_INDEX, "replay: an index outside [0, filled) was given");
+    return TQ_OK;
+}
+#define RHANDLE(r)                                                \
+    DeviceGuard _guard;                                           \
+    if (!(r)) return fail(TQ_E_INVALID, "NULL replay handle");    \
+    if (int _rc = _guard.enter_device((r)->device)) return _rc;   \
+    hipStream_t stream = (hipStream_t)stream_
+
+// canonical rebuild of the whole tree: every chunk, then the top levels
+int replay_rebuild_all(tq_replay* r, hipStream_t stream) {
+    hipLaunchKernelGGL(tq::k_replay_chunks, dim3((unsigned)r->nchunks), dim3(256), 0, stream, r->tree, r->L, r->clg,
+                       r->nchunks, (const tq::ReplayDev*)r->st, 0);
+    hipLaunchKernelGGL(tq::k_replay_top, dim3(1), dim3(1024), 0, stream, r->tree, r->L - 1 - r->clg, r->st,
+                       (const int64_t*)nullptr, r->cap);
+    KCHECK();
+    return TQ_OK;
+}
+
+// scatter update with last-wins + rebuild of the touched paths (or of the whole tree when that is less work)
+int replay_update(tq_replay* r, const int64_t* idx, const double* p, int64_t n, hipStream_t stream) {
+    const unsigned long long serial = ++r->serial;
+    hipLaunchKernelGGL(tq::k_replay_stamp, grid1(n, 256), dim3(256), 0, stream, idx, n, r->stamp, serial, r->st);
+    hipLaunchKernelGGL(tq::k_replay_scatter, grid1(n, 256), dim3(256), 0, stream, idx, p, n,
+                       (const unsigned long long*)r->stamp, serial, r->tree + ((int64_t(1) << (r->L - 1)) - 1), r->alpha,
+                       (const tq::ReplayDev*)r->st);
+    KCHECK();
+    if (n * 64 >= r->cap) return replay_rebuild_all(r, stream);
+    hipLaunchKernelGGL(tq::k_replay_paths, dim3(1), dim3(1024), 0, stream, idx, n, r->tree, r->L, (const tq::ReplayDev*)r->st);
+    KCHECK();
+    return TQ_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int tq_replay_create(tq_replay** out, int d, int64_t capacity, double alpha, int device, uint64_t seed, int faithful) {
+    if (!out) return fail(TQ_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (!size_ok(d)) return fail(TQ_E_INVALID, "unsupported lattice size d=%d (odd 3..21)", d);
+    if (capacity < 1 || capacity > tq::RP_MAX_CAPACITY)
+        return fail(TQ_E_INVALID, "replay capacity must be in 1..%lld (got %lld)", (long long)tq::RP_MAX_CAPACITY, (long long)capacity);
+    if (!(alpha >= 0.0) || alpha > 1e300) return fail(TQ_E_INVALID, "alpha must be a finite number >= 0");
+    if (faithful != 0 && faithful != 1) return fail(TQ_E_INVALID, "faithful must be 0 or 1");
+    int ndev = 0;
+    HIPCHECK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev || device >= MAX_DEVICES)
+        return fail(TQ_E_INVALID, "device %d not available (%d HIP devices)", device, ndev);
+    DeviceGuard guard;
+    if (int rc = guard.enter_device(device)) return rc;
+    tq_replay* r = new (std::nothrow) tq_replay();
+    if (!r) return fail(TQ_E_INVALID, "out of host memory");
+    memset(r, 0, sizeof(*r));
+    r->d = d; r->w = (d * d + 63) / 64; r->device = device; r->faithful = faithful;
+    r->cap = capacity; r->alpha = alpha; r->seed = seed;
+    r->L = replay_levels(capacity);
+    r->clg = r->L - 1 < tq::RP_CHUNK_LG ? r->L - 1 : tq::RP_CHUNK_LG;
+    r->nchunks = (capacity + (int64_t(1) << r->clg) - 1) >> r->clg;
+    hipError_t e = hipSuccess;
+    auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); if (e == hipSuccess) e = hipMemset(*p, 0, bytes); };
+    alloc((void**)&r->tree, ((size_t(1) << r->L) - 1) * sizeof(double));
+    alloc(&r->ring, (size_t)tq::ring_bytes(r->w, capacity));
+    alloc((void**)&r->st, sizeof(tq::ReplayDev));
+    alloc((void**)&r->stamp, (size_t)capacity * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+    if (e != hipSuccess) { tq_replay_destroy(r); return fail(TQ_E_HIP, "replay allocation failed: %s", hipGetErrorString(e)); }
+    *out = r;
+    return TQ_OK;
+}
+
+int tq_replay_destroy(tq_replay* r) {
+    if (!r) return TQ_OK;
+    DeviceGuard guard;
+    (void)guard.enter_device(r->device);
+    (void)hipFree(r->tree); (void)hipFree(r->ring); (void)hipFree(r->st); (void)hipFree(r->stamp);
+    (void)hipFree(r->flags); (void)hipFree(r->partial); (void)hipFree(r->offsets);
+    (void)hipGetLastError();
+    delete r;
+    return TQ_OK;
+}
+
+int tq_replay_save_block(tq_replay* r, const void* block, int64_t cap, void* stream_) {
+    RHANDLE(r);
+    if (!block || cap < 0) return fail(TQ_E_INVALID, "bad block / cap");
+    if (reinterpret_cast<uintptr_t>(block) & 7u) return fail(TQ_E_INVALID, "block must be 8-byte aligned");
+    if (cap == 0) return TQ_OK;
+    if (cap > r->scratch_cap) {            // grows once per larger block (allocates, synchronises)
+        HIPCHECK(hipStreamSynchronize(stream));
+        (void)hipFree(r->flags); (void)hipFree(r->partial); (void)hipFree(r->offsets);
+        r->flags = nullptr; r->partial = nullptr; r->offsets = nullptr; r->scratch_cap = 0;
+        HIPCHECK(hipMalloc((void**)&r->flags, (size_t)cap * 4 + 32));
+        HIPCHECK(hipMalloc((void**)&r->partial, (size_t)((cap + tq::PART_BLOCK - 1) / tq::PART_BLOCK) * 8));
+        HIPCHECK(hipMalloc((void**)&r->offsets, (size_t)(cap + 1) * 8));
+        r->scratch_cap = cap;
+    }
+    tq::BlockView b = tq::block_view(const_cast<void*>(block), r->w, cap);
+    tq::RingView ring = tq::ring_view(r->ring, r->w, r->cap);
+    hipLaunchKernelGGL(tq::k_replay_flags, grid1(cap, 256), dim3(256), 0, stream, (const uint32_t*)b.action, cap, r->flags);
+    KCHECK();
+    if (int rc = launch_scan(r->flags, r->partial, false, r->offsets, nullptr, cap, stream, nullptr)) return rc;
+    double* leaves = r->tree + ((int64_t(1) << (r->L - 1)) - 1);
+    hipLaunchKernelGGL(tq::k_replay_ingest, grid1(cap, 256), dim3(256), 0, stream, b, (const int64_t*)r->offsets, ring, r->w,
+                       leaves, r->alpha, (const tq::ReplayDev*)r->st);
+    // The touched positions start at the cursor and span at most min(cap, capacity), modulo the capacity.  Counted in
+    // chunk slots, a range that wraps also crosses the unused tail of the last chunk (nchunks * 2^clg - capacity
+    // leaves): so the chunks to rebuild are those of span + tail consecutive slots -- that many chunks and one more.
+    const int64_t span = cap < r->cap ? cap : r->cap;
+    const int64_t tail = (r->nchunks << r->clg) - r->cap;
+    int64_t nch = ((span + tail + (int64_t(1) << r->clg) - 1) >> r->clg) + 1;
+    if (nch > r->nchunks) nch = r->nchunks;
+    hipLaunchKernelGGL(tq::k_replay_chunks, dim3((unsigned)nch), dim3(256), 0, stream, r->tree, r->L, r->clg, r->nchunks,
+                       (const tq::ReplayDev*)r->st, 1);
+    hipLaunchKernelGGL(tq::k_replay_top, dim3(1), dim3(1024), 0, stream, r->tree, r->L - 1 - r->clg, r->st,
+                       (const int64_t*)(r->offsets + cap), r->cap);
+    KCHECK();
+    return TQ_OK;
+}
+
+int64_t tq_replay_filled(tq_replay* r, void* stream_) {
+    RHANDLE(r);
+    int64_t filled = 0;
+    HIPCHECK(hipMemcpyAsync(&filled, &r->st->filled, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    return filled;
+}
+
+int tq_replay_get(tq_replay* r, const int64_t* indices, int n, float* state, float* next_state, int64_t* actions_idx,
+                  float* rewards, uint8_t* terminals, int32_t* actions, void* stream_) {
+    RHANDLE(r);
+    if (n < 0 || (n > 0 && !indices)) return fail(TQ_E_INVALID, "bad indices / n");
+    if (n == 0) return TQ_OK;
+    tq::RingView ring = tq::ring_view(r->ring, r->w, r->cap);
+    const int64_t total = (int64_t)n * 2 * r->d * r->d;
+#define CALL(D) hipLaunchKernelGGL(tq::k_replay_gather<D>, grid1(total, 256), dim3(256), 0, stream, ring, indices, (int64_t)n, \
+        r->st, state, next_state, actions_idx, rewards, terminals, actions)
+    DISPATCH_D(r->d, CALL)
+#undef CALL
+    KCHECK();
+    return TQ_OK;
+}
+
+int tq_replay_sample(tq_replay* r, int batch, double beta, const double* uniforms, int64_t* indices, double* priorities,
+                     double* weights, float* state, float* next_state, int64_t* actions_idx, float* rewards,
+                     uint8_t* terminals, int32_t* actions, void* stream_) {
+    RHANDLE(r);
+    if (batch < 1 || batch > tq::RP_MAX_BATCH) return fail(TQ_E_INVALID, "batch must be in 1..%d (got %d)", tq::RP_MAX_BATCH, batch);
+    if (!indices || !priorities || !weights) return fail(TQ_E_INVALID, "indices / priorities / weights is NULL");
+    if (!(beta == beta)) return fail(TQ_E_INVALID, "beta is NaN");
+    const uint64_t call = uniforms ? 0 : r->calls++;
+    hipLaunchKernelGGL(tq::k_replay_sample, dim3(1), dim3(256), 0, stream, (const double*)r->tree, r->L, r->cap, batch, beta,
+                       uniforms, r->seed, call, indices, priorities, weights, r->st);
+    KCHECK();
+    if (state || next_state || actions_idx || rewards || terminals || actions)
+        if (int rc = tq_replay_get(r, indices, batch, state, next_state, actions_idx, rewards, terminals, actions, stream_)) return rc;
+    if (r->faithful) return replay_update(r, indices, priorities, batch, stream);    // the reference's revert (:119)
+    return TQ_OK;
+}
+
+int tq_replay_update(tq_replay* r, const int64_t* indices, const double* priorities, int n, void* stream_) {
+    RHANDLE(r);
+    if (n < 0 || (n > 0 && (!indices || !priorities))) return fail(TQ_E_INVALID, "bad indices / priorities / n");
+    if (n == 0) return TQ_OK;
+    return replay_update(r, indices, priorities, n, stream);
+}
+
+int tq_replay_reset_alpha(tq_replay* r, double alpha, void* stream_) {
+    RHANDLE(r);
+    if (!(alpha >= 0.0) || alpha > 1e300) return fail(TQ_E_INVALID, "alpha must be a finite number >= 0");
+    if (!r->faithful && r->alpha == 0.0) return fail(TQ_E_INVALID, "reset_alpha: alpha 0 cannot be inverted");
+    double* leaves = r->tree + ((int64_t(1) << (r->L - 1)) - 1);
+    hipLaunchKernelGGL(tq::k_replay_realpha, grid1(r->cap, 256), dim3(256), 0, stream, leaves, (const tq::ReplayDev*)r->st,
+                       r->alpha, alpha, r->faithful);
+    KCHECK();
+    r->alpha = alpha;
+    return replay_rebuild_all(r, stream);
+}
+
+int tq_replay_leaves(tq_replay* r, double* out, void* stream_) {
+    RHANDLE(r);
+    if (!out) return fail(TQ_E_INVALID, "out is NULL");
+    HIPCHECK(hipMemcpyAsync(out, r->tree + ((int64_t(1) << (r->L - 1)) - 1), (size_t)r->cap * sizeof(double),
+                            hipMemcpyDeviceToDevice, stream));
+    return TQ_OK;
+}
+
+int64_t tq_replay_tree_nodes(const tq_replay* r) {
+    if (!r) return fail(TQ_E_INVALID, "NULL replay handle");
+    return (int64_t(1) << r->L) - 1;
+}
+
+int tq_replay_tree(tq_replay* r, double* out, void* stream_) {
+    RHANDLE(r);
+    if (!out) return fail(TQ_E_INVALID, "out is NULL");
+    HIPCHECK(hipMemcpyAsync(out, r->tree, (size_t)tq_replay_tree_nodes(r) * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    return TQ_OK;
+}
+
+int tq_replay_check(tq_replay* r, void* stream_) {
+    RHANDLE(r);
+    int flag = 0;
+    HIPCHECK(hipMemcpyAsync(&flag, &r->st->err, sizeof(int), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (flag) HIPCHECK(hipMemsetAsync(&r->st->err, 0, sizeof(int), stream));
+    return replay_latch(flag);
 }
 
 }  // extern "C"
