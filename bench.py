@@ -28,22 +28,28 @@ touches the GPU) and relays rank 0's JSON line; under torch.distributed.run (WOR
 per GPU; every rank owns a contiguous block of global env ids (weak scaling).  Default shape for N>1: BASELINE.json
 configs[4] -- 131 072 lattices per GPU, and every transition (with its priority) is delivered to the HOST replay ring:
 RCCL gather of the packed blocks to rank 0 over xGMI every --flush steps (issued from stream B right behind the
-priorities), then rank 0's copy stream drains each gathered slot to pinned host memory.  The rate with the ring kept in
-rank 0's HBM is measured right after and reported beside it (`hbm_ring`); `ranks[]` carries every rank's own roofline.
+priorities), then rank 0's copy stream drains each gathered slot to pinned host memory.  With --full the rate with the
+ring kept in rank 0's HBM is measured right after and reported beside it (`hbm_ring`); `ranks[]` carries every rank's
+own roofline.
 
 Prints ONE JSON line on rank 0 (contract in the task statement), under 8 KiB: the full record, with every side leg's probe
 report, goes to stderr as `[bench] full record: {...}` and the line keeps of a side leg its rate, `frac`, `timed_over_probe`
 and `stack_verified` (result_line).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).
-Every leg -- the headline, `configs4_shard_on_one_gpu`,
-`bf16_stack`, `configs3_on_one_gpu.{one_shot,chunks_4}` -- carries `stack_buffer_probe`, `stack_verified` (the timed buffer
-holds the right bytes; a failure voids the line) and its own `roofline` (HIP events on the write's stream around every
---event-every-th write; `probe_ms_chosen`, `timed_write_ms`, `timed_over_probe`, `default_buffer`, `workgroup_shares` = the XCD bias in force and the probe's biased-against-equal timing); `cpu_baseline` (the
-oracle's ports on the host cores, rank 0, N=1 only) and `nn_in_loop` (configs[2] as written: the stack fed to NN_11 and
-device-side selection in the loop; N=1 only, --nn-steps 0 to skip).  --shards > 1, --graph and --policy nn11 take the
-serial path (run_serial).
+
+A plain run measures the headline alone: set-up, warm-up, the timed steps, `stack_verified`, the `roofline` from the timed
+steps' own events, --dump-outputs, the line.  --full adds everything else, after the headline's timed region: the side
+legs `configs4_shard_on_one_gpu`, `bf16_stack` and `configs3_on_one_gpu.{one_shot,chunks_4}` (N=1, default shape;
+--no-shard-leg to skip), `nn_in_loop` (configs[2] as written: the stack fed to NN_11 and device-side selection in the
+loop; N=1 only, --nn-steps 0 to skip), `cpu_baseline` (the oracle's ports on the host cores, rank 0, N=1 only,
+--cpu-seconds 0 to skip), `hbm_ring` (N>1) and the roofline's `measured_fill_gbps` and profiled `traffic`.
+Every leg carries `stack_buffer_probe`, `stack_verified` (the timed buffer holds the right bytes; a failure voids the line)
+and its own `roofline` (HIP events on the write's stream around every --event-every-th write; `probe_ms_chosen`,
+`timed_write_ms`, `timed_over_probe`, `default_buffer`, `workgroup_shares` = the XCD bias in force and the probe's
+biased-against-equal timing).  --shards > 1, --graph and --policy nn11 take the serial path (run_serial).
 """
 import argparse
 import contextlib
+import ctypes
 import gc
 import json
 import os
@@ -108,18 +114,21 @@ def parse(argv=None):
                          "torch.empty, chunked = T.alloc_stack (2 MiB physical "
                          "chunks, tq_stack_alloc).  Profile runs use --stack-candidates 1 --stack-kinds chunked so that every "
                          "launch of the process writes the same buffer")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check what it does not need: the side legs of the N=1 line, "
+                         "nn_in_loop, cpu_baseline, the N>1 HBM-ring rate, the roofline's fill rate and profiled traffic")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget (0 = skip)")
     ap.add_argument("--nn-steps", type=int, default=3,
-                    help="N=1: timed steps of the NN_11-in-the-loop leg (configs[2] as written); 0 = skip")
+                    help="--full, N=1: timed steps of the NN_11-in-the-loop leg (configs[2] as written); 0 = skip")
     ap.add_argument("--no-shard-leg", action="store_true",
-                    help="N=1: skip the extra timing of the N>1 per-GPU shape (131072 lattices); profiling runs use this "
-                         "so that every k_persp_stream launch of the process has the headline shape")
+                    help="--full, N=1: skip the extra legs on other shapes and dtypes (configs[4] shard, bf16 stack, configs[3]); "
+                         "profiling runs use this so that every k_persp_stream launch of the process has the headline shape")
     ap.add_argument("--no-events", action="store_true", help="no per-launch HIP events (pure wall clock)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="default path: run the fused step and the scan BEHIND the stack write on one stream (the reference's order) "
                          "instead of beside it on a second stream (T.ExploreLoop)")
     ap.add_argument("--bf16-steps", type=int, default=20,
-                    help="N=1: timed steps of the bf16-stack leg (the stack the bf16 nn_in_loop variant consumes), with its own roofline; 0 = skip")
+                    help="--full, N=1: timed steps of the bf16-stack leg (the stack the bf16 nn_in_loop variant consumes), with its own roofline; 0 = skip")
     ap.add_argument("--graph", action="store_true",
                     help="capture --flush steps in a HIP graph and replay it (launch-bound small batches; implies "
                          "--no-events: no per-launch timing inside a graph, so no roofline object)")
@@ -497,7 +506,8 @@ class ExploreLeg:
                 "how": "after the timed region: stack + positions of the current lattices written into the timed buffer and into "
                        "a fresh torch.empty buffer, compared byte for byte"}
 
-    def close(self):
+    def close(self, wait=True):
+        """``wait``: another leg is timed next (the driver wipes freed memory in the background)."""
         if self.loop is not None:
             self.loop.drain()
         self.torch.cuda.synchronize(self.device)       # nothing of the side stream may still run when the handle goes
@@ -506,7 +516,8 @@ class ExploreLeg:
         self.loop = None
         self.stack = None
         self.torch.cuda.empty_cache()
-        time.sleep(0.5)                         # ... and the driver wipes freed memory in the background
+        if wait:
+            time.sleep(0.5)                     # ... and the driver wipes freed memory in the background
 
 
 def time_explore_leg(T, torch, env, n, d, seed, tdtype, flush, device, steps, warm, chunks=1, candidates=1, kinds=("torch", "chunked"),
@@ -651,6 +662,15 @@ def print_result(res, result_out):
     print(line, file=result_out, flush=True)
 
 
+def keep_until_exit(envs):
+    """A plain run: the stack-buffer probe's parked candidates are never freed by this process -- their references are
+    leaked, so no destructor frees them and the driver takes the memory back when the process exits.  The probe parks
+    23 or, when it extends its search, 47 buffers of 2.5 GB at d=7, and tq_stack_free unmaps a buffer chunk by chunk,
+    1 200 chunks of 2 MiB: 4.5 s for 23 candidates, 16 s for 47 on MI355X; the exit with 40 of them mapped takes 0.8 s."""
+    for x in getattr(envs, "_parked", []):
+        ctypes.pythonapi.Py_IncRef(ctypes.py_object(x))
+
+
 def load_trained_weights(d):
     """The reference's trained NN_11 state_dict for size d, committed as a data fixture (tests/golden/nn11_d*.safetensors,
     made by tests/golden/make_weights.py from network/converged/*.pt with weights_only=True), or None."""
@@ -691,6 +711,25 @@ def pmc_traffic(d, out_dtype, n, p_error, launches_per_step, p_mean):
     except Exception:
         pass
     return None, None
+
+
+def roofline_context(torch, stack, alg, achieved, pmc):
+    """--full: what a `roofline` is read against beyond the peak -- the counter traffic of a profiled run of the same shape
+    (pmc_traffic) and the box's own streaming-fill bandwidth, measured after the timed region on the same
+    buffer (hipMemsetAsync through torch)."""
+    traffic, ent = pmc
+    fb = stack.view(torch.uint8).reshape(-1)[:int(alg) & ~4095]
+    f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    fill_ms = []
+    for _ in range(6):
+        f0.record(); fb.zero_(); f1.record(); f1.synchronize()
+        fill_ms.append(f0.elapsed_time(f1))
+    fill_gbps = fb.numel() / (min(fill_ms[1:]) * 1e-3) / 1e9
+    return {"traffic": traffic, "traffic_over_algorithmic": None if traffic is None else traffic / alg,
+            "traffic_from_profile_run": None if ent is None else True,
+            "traffic_source": None if ent is None else "%s; counters of the profiled run %s, not of this process" % (
+                ent.get("source"), ent.get("profiled_at", "profiles/pmc_latest.json")),
+            "measured_fill_gbps": fill_gbps, "frac_of_measured_fill": achieved / fill_gbps}
 
 
 def dry_run(args, world, rank, result_out):
@@ -772,7 +811,6 @@ def run_explore(ctx):
     import torch.distributed as dist
     import toric_rl_decoder_amd as T
     from toric_rl_decoder_amd import gather as G
-    from toric_rl_decoder_amd.policy import _forward_chunked
     args, world, rank, device, red_dev, dist_on, backend, result_out = (ctx.args, ctx.world, ctx.rank, ctx.device, ctx.red_dev, ctx.dist_on,
                                                                          ctx.backend, ctx.result_out)
     d, K, W = args.size, args.steps, args.warmup
@@ -876,9 +914,9 @@ def run_explore(ctx):
         rank_rows = [{"rank": r, "frac": float(x[0]), "avg_launch_ms": float(x[1]), "probe_ms_chosen": num(x[2]), "timed_over_probe": num(x[3]),
                       "perspectives_per_launch": float(x[4]), "stack_verified": bool(x[5] > 0.5)} for r, x in enumerate(allr)]
 
-    # ---- N>1 with host delivery: the same region again with the ring kept in rank 0's HBM
+    # ---- N>1 with host delivery (--full): the same region again with the ring kept in rank 0's HBM
     hbm_ring = None
-    if host_delivery:
+    if host_delivery and args.full:
         state["tg"] = make_gather(False)
         warm_collective(state["tg"])
         barrier()
@@ -886,10 +924,13 @@ def run_explore(ctx):
         hbm_ring = {"value": total_steps / el2, "ms_per_step": 1e3 * el2 / K,
                     "note": "same run, transition ring left in rank 0's HBM (no D2H drain)"}
     state["tg"] = None
-    leg.envs.releaseParked()
-    time.sleep(0.5)
+    if args.full:                       # room for the legs that follow, and the driver wipes what was freed before they are timed
+        leg.envs.releaseParked()
+        time.sleep(0.5)
+    else:
+        keep_until_exit(leg.envs)
 
-    n1_legs = world == 1 and not dist_on and args.envs is None and not args.no_shard_leg and CH == 1
+    n1_legs = args.full and world == 1 and not dist_on and args.envs is None and not args.no_shard_leg and CH == 1
     # ---- N=1 on the default shape: one GPU on the per-GPU shape of the N>1 runs (configs[4]), like for like
     shard_leg = None
     if n1_legs:
@@ -924,8 +965,8 @@ def run_explore(ctx):
     # ---- N=1: configs[2] as written -- generatePerspective feeding NN_11 for selectAction, measured at size in
     # f32 (what upstream runs) and with the bf16 stack the kernels can write directly + bf16 autocast
     nn_leg = None
-    if world == 1 and args.nn_steps > 0 and CH == 1:
-        from toric_rl_decoder_amd.policy import NN_11
+    if args.full and world == 1 and args.nn_steps > 0 and CH == 1:
+        from toric_rl_decoder_amd.policy import NN_11, _forward_chunked
         flop_per_persp = 2.0 * sum(ci * co * 9 * ((d - 2) ** 2 if i == 10 else d * d)
                                    for i, (ci, co) in enumerate(zip((2, 128, 128, 120, 111, 104, 103, 90, 80, 73, 71),
                                                                     (128, 128, 120, 111, 104, 103, 90, 80, 73, 71, 64))))
@@ -1033,22 +1074,9 @@ def run_explore(ctx):
         if c3_leg is not None:
             res["configs3_on_one_gpu"] = c3_leg
         if roof is not None:
-            alg = roof["bytes_per_step"]
-            traffic, ent = pmc_traffic(d, args.out_dtype, n, args.p_error, CH, p_mean)
-            # context: the box's own streaming-fill bandwidth, measured after the timed region
-            # on the same buffer (hipMemsetAsync through torch), so frac can be read against it as well
-            fb = leg.stack.view(torch.uint8).reshape(-1)[:int(alg) & ~4095]
-            f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            fill_ms = []
-            for _ in range(6):
-                f0.record(); fb.zero_(); f1.record(); f1.synchronize()
-                fill_ms.append(f0.elapsed_time(f1))
-            fill_gbps = fb.numel() / (min(fill_ms[1:]) * 1e-3) / 1e9
-            roof.update({"traffic": traffic, "traffic_over_algorithmic": None if traffic is None else traffic / alg,
-                         "traffic_from_profile_run": None if ent is None else True,
-                         "traffic_source": None if ent is None else "%s; counters of the profiled run %s, not of this process" % (
-                             ent.get("source"), ent.get("profiled_at", "profiles/pmc_latest.json")),
-                         "measured_fill_gbps": fill_gbps, "frac_of_measured_fill": roof["achieved"] / fill_gbps})
+            if args.full:
+                roof.update(roofline_context(torch, leg.stack, roof["bytes_per_step"], roof["achieved"],
+                                             pmc_traffic(d, args.out_dtype, n, args.p_error, CH, p_mean)))
             res["roofline"] = roof
             res["non_write_us_per_step"] = 1e3 * (res["ms_per_step"] - roof["avg_launch_ms"])
         # every leg's timed write against what its probe promised: the legs outside 3 % are named
@@ -1069,14 +1097,14 @@ def run_explore(ctx):
             res["void_legs"] = bad_legs
         if nn_leg is not None:
             res["nn_in_loop"] = nn_leg
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             res["cpu_baseline"] = cpu_baseline(d, args.p_error, args.seed, args.cpu_seconds)
         if dumped is not None:
             res["dumped_outputs"] = {"dir": args.dump_outputs, "files": len(dumped), "bytes": sum(dumped.values())}
         print_result(res, result_out)
         if void:
             print("[bench] THE TIMED STACK BUFFER HOLDS WRONG BYTES (%d): the numbers of this run are void" % verified["wrong_bytes"], file=sys.stderr, flush=True)
-    leg.close()
+    leg.close(wait=False)
     if dist_on:
         dist.destroy_process_group()
     if not verified["ok"]:
@@ -1284,8 +1312,12 @@ def run_serial(ctx):
     elapsed = timed_region(0)
     for sh in shards:
         sh.envs.check()                                               # capacity / action / reset latch
-        sh.envs.releaseParked()
-    time.sleep(0.5)
+        if args.full:
+            sh.envs.releaseParked()
+        else:
+            keep_until_exit(sh.envs)
+    if args.full:
+        time.sleep(0.5)
 
     if graph is not None:      # slot t of the captured window accumulated its P over the K/flush replays
         p_timed = (p_acc.to(torch.float64) / (K // flush)).repeat(K // flush).reshape(1, -1)
@@ -1322,9 +1354,9 @@ def run_serial(ctx):
         if wrong:
             print("[bench] THE TIMED STACK BUFFER HOLDS WRONG BYTES (%d): the numbers of this run are void" % wrong, file=sys.stderr, flush=True)
 
-    # ---- N>1 with host delivery: the same region again with the ring kept in rank 0's HBM
+    # ---- N>1 with host delivery (--full): the same region again with the ring kept in rank 0's HBM
     hbm_ring = None
-    if host_delivery and graph is None:
+    if host_delivery and graph is None and args.full:
         state["tg"] = make_gathers(False)
         warm_collective(state["tg"])
         barrier()
@@ -1375,32 +1407,20 @@ def run_serial(ctx):
             p_mean = float(p_timed[:, ::EV].mean().item())              # of the launches the events bracket
             alg = p_mean * (nq * esize + 12) + ns * nq                 # P*(B_p+12) + N*2d^2, per launch
             achieved = alg / (ev_ms.mean() * 1e-3) / 1e9
-            traffic, ent = pmc_traffic(d, args.out_dtype, n, args.p_error, S * CH, p_mean)
-            # context: the box's own streaming-fill bandwidth, measured after the timed region
-            # on the same buffer (hipMemsetAsync through torch), so frac can be read against it as well
-            fb = shards[0].stack.view(torch.uint8).reshape(-1)[:int(alg) & ~4095]
-            f0, f1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            fill_ms = []
-            for _ in range(6):
-                f0.record(); fb.zero_(); f1.record(); f1.synchronize()
-                fill_ms.append(f0.elapsed_time(f1))
-            fill_gbps = fb.numel() / (min(fill_ms[1:]) * 1e-3) / 1e9
             res["roofline"] = {"bound": "hbm", "kernel": STACK_KERNEL, "achieved": achieved, "peak": HBM_PEAK_GBPS,
-                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                               "traffic_over_algorithmic": None if traffic is None else traffic / alg,
-                               "traffic_from_profile_run": None if ent is None else True,
-                               "traffic_source": None if ent is None else "%s; counters of the profiled run %s, not of this process" % (
-                                   ent.get("source"), ent.get("profiled_at", "profiles/pmc_latest.json")),
-                               "measured_fill_gbps": fill_gbps, "frac_of_measured_fill": achieved / fill_gbps,
+                               "unit": "GB/s", "frac": achieved / HBM_PEAK_GBPS,
                                "bytes_per_launch": alg, "avg_launch_ms": float(ev_ms.mean()),
                                "median_launch_ms": float(np.median(ev_ms)), "perspectives_per_launch": p_mean,
                                "launches_per_step": S * CH, "lattices_per_launch": ns // CH,
                                "launches_timed": int(ev_ms.size),
                                "timed_launches": "every %d%s step of the timed region (a HIP event record costs ~3 us of stream time; "
                                                  "--event-every 1 brackets every launch)" % (EV, "th" if EV > 3 else ("st", "nd", "rd")[EV - 1])}
+            if args.full:
+                res["roofline"].update(roofline_context(torch, shards[0].stack, alg, achieved,
+                                                        pmc_traffic(d, args.out_dtype, n, args.p_error, S * CH, p_mean)))
         if nn_leg is not None:
             res["nn_in_loop"] = nn_leg
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full and world == 1 and args.cpu_seconds > 0:
             res["cpu_baseline"] = cpu_baseline(d, args.p_error, args.seed, args.cpu_seconds)
         print_result(res, result_out)
     for sh in shards:

@@ -111,12 +111,12 @@ def test_bench_two_ranks_share_the_gpu():
 def test_bench_rccl_path_keeps_stdout_to_one_line():
     """The collective path over RCCL (a world of one rank on this box, TORIC_FORCE_DIST=1) with delivery to
     the pinned host ring: RCCL prints its version banner on stdout when the communicator comes up -- the
-    bench must still print exactly one line there -- and the line carries the HBM-ring rate beside it."""
+    bench must still print exactly one line there -- and with --full the line carries the HBM-ring rate beside it."""
     env = dict(os.environ, TORIC_FORCE_DIST="1", MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):   # no port given: bench.py picks a free one
         env.pop(k, None)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "16", "--warmup", "8", "--envs", "32768",
-                        "--cpu-seconds", "0", "--nn-steps", "0"], capture_output=True, text=True, timeout=600, env=env)
+                        "--cpu-seconds", "0", "--nn-steps", "0", "--full"], capture_output=True, text=True, timeout=600, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, p.stdout[:500]
@@ -131,7 +131,7 @@ def test_bench_rccl_path_keeps_stdout_to_one_line():
 @pytest.mark.gpu
 def test_bench_json_contract():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--envs", "8192",
-                        "--cpu-seconds", "0.5", "--nn-steps", "1"], capture_output=True, text=True, timeout=600)
+                        "--cpu-seconds", "0.5", "--nn-steps", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1 and len(lines[0]) < 8192
@@ -170,6 +170,24 @@ def test_bench_json_contract():
     assert r["kernel"] == "k_persp_stream" and "custom" in j["config"]["workload"]      # 8192 lattices: not a BASELINE config
     assert j["config"]["steady_state"] is True and 40 < j["perspectives_per_lattice"] < 98
     assert j["value"] > 1e6 and abs(j["value"] - 8192 * 6 / (j["ms_per_step"] * 6e-3)) / j["value"] < 1e-6
+
+
+@pytest.mark.gpu
+def test_plain_run_measures_the_headline_alone():
+    """Without --full the run does what its headline needs and no more: the contract's keys, the roofline from the timed
+    steps' own events and the check of the timed buffer -- no CPU baseline, no NN leg, no fill measurement."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--envs", "8192"],
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 8192
+    j = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "roofline", "stack_verified"} <= set(j)
+    assert not {"cpu_baseline", "nn_in_loop", "hbm_ring", "configs4_shard_on_one_gpu", "bf16_stack", "configs3_on_one_gpu"} & set(j)
+    r = j["roofline"]
+    assert "measured_fill_gbps" not in r and "traffic" not in r and r["frac"] > 0 and r["timed_over_probe"] > 0
+    assert j["steps"] == 6 and j["warmup"] == 2 and j["stack_verified"]["ok"] is True and j["probe_vs_timed"].keys() == {"headline"}
+    assert abs(j["value"] - 8192 * 6 / (j["ms_per_step"] * 6e-3)) / j["value"] < 1e-6
 
 
 @pytest.mark.gpu

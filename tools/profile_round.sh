@@ -1,7 +1,7 @@
 #!/bin/bash
 # One profiled configuration, on the GPU box (through gpurun):
 #   tools/profile_round.sh <tag> [bench args...]
-# -> gpurun_out/<tag>/bench.json            plain `python3 bench.py <args>` line
+# -> $OUT/bench.json                        the `python3 bench.py --full <args>` line, every leg
 #    gpurun_out/<tag>/kernel_stats.csv      rocprofv3 --kernel-trace --stats summary of the SAME command
 #    gpurun_out/<tag>/kernel_trace_timed_region.txt   the stack write's dispatches of the timed region alone (tools/trace_tail.py)
 #    gpurun_out/<tag>/bench_under_rocprof.json   the line that very run printed
@@ -14,8 +14,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd "$REPO"
-echo "[$TAG] plain bench"
-python3 bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
+echo "[$TAG] bench --full"
+python3 bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "[$TAG] kernel trace"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 "$REPO/bench.py" "$@" --cpu-seconds 0 --nn-steps 0 --no-shard-leg \
