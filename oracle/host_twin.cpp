@@ -6,10 +6,13 @@
 // It is NOT part of the product and the product never loads it: toric-rl-decoder_amd/ has exactly one compute path,
 // libtoricenv.so (HIP).  Only tests/ and bench.py's cpu_baseline leg use this file (through oracle/host_twin.py).
 //
-// What it is made of: the product's own host+device header csrc/lattice.hpp (bit-plane lattice algebra, Philox
-// contract, reset samplers, the perspective closed forms) plus a scalar restatement of the kernels around it, each
-// citing the device code it follows.  So tests of the twin against the numpy / C oracle check the product's HEADER on
-// a machine without a GPU, and the twin's throughput is the same-ABI, same-algorithm CPU number.
+// What it is made of: the product's own host+device headers -- csrc/lattice.hpp (bit-plane lattice algebra, Philox
+// contract, reset samplers, the perspective closed forms) and csrc/env_step.hpp (what a step does to one lattice: the
+// exploration draw, apply / syndrome / reward / terminal, the transition record, the p_error schedule) -- inside an ABI
+// shell of its own: the handle, validation, one OpenMP loop per entry point, a plain call of reset_lattice where the
+// GPU resets wave-cooperatively, and an independent scalar writer of the perspective stack.  So tests of the twin
+// against the numpy / C oracle check the per-lattice code the kernels compile, on a machine without a GPU, and the
+// twin's throughput is the same-ABI, same-algorithm CPU number.
 //
 // Entry points present: tq_version, tq_last_error, tq_create, tq_destroy, tq_set_params, tq_set_min_qubit_errors,
 // tq_set_perror_schedule, tq_num_envs, tq_size, tq_reset_all, tq_get_state, tq_get_qubits, tq_get_counters,
@@ -24,7 +27,7 @@
 #include <vector>
 
 #include "toricenv.h"
-#include "lattice.hpp"
+#include "env_step.hpp"
 
 using namespace tq;
 
@@ -37,21 +40,16 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
-// device error latch bits (csrc/kernels.hpp:28)
-enum { ERR_ACTION = 1, ERR_CAPACITY = 2, ERR_RESET_ROUNDS = 8 };
-enum { PL_X0 = 0, PL_X1 = 1, PL_Z0 = 2, PL_Z1 = 3, PL_V = 4, PL_P = 5 };
-int64_t align8(int64_t x) { return (x + 7) & ~(int64_t)7; }
 }  // namespace
 
 struct tq_env {
     int n, d, w;
     uint64_t seed;
     int64_t first_env;
-    double p_default, terminal_reward;
+    PerrSchedule sched;
+    double terminal_reward;
     int max_steps, min_err;
-    int strategy;
-    double p_start, p_final, p_delta;
-    std::vector<uint64_t> planes;      // [6][W][N], as in HBM (csrc/kernels.hpp:3-7)
+    std::vector<uint64_t> planes;      // [6][W][N], as in HBM (header comment of csrc/kernels.hpp)
     std::vector<uint32_t> episodes, steps;
     std::vector<int32_t> counts;
     std::vector<double> p_roof;
@@ -82,17 +80,7 @@ void store_state(tq_env* h, int64_t e, const typename Lat<D>::State& s) {
     }
 }
 
-// k-th set bit of [E0 | E1] as layer*DD + row*D + col (csrc/kernels.hpp:67-103; plain loop here)
-template <int D>
-int kth_hit(const typename Lat<D>::B& e0, const typename Lat<D>::B& e1, int k) {
-    constexpr int DD = Lat<D>::DD;
-    for (int l = 0; l < 2; ++l)
-        for (int c = 0; c < DD; ++c)
-            if ((l ? e1.get(c) : e0.get(c)) && k-- == 0) return l * DD + c;
-    return -1;
-}
-
-// tq_reset_all: k_reset, all-lattice mode (csrc/kernels.hpp:131-162)
+// tq_reset_all: k_reset, all-lattice mode
 template <int D>
 int reset_all(tq_env* h, const double* p_err) {
     using L = Lat<D>;
@@ -102,7 +90,7 @@ int reset_all(tq_env* h, const double* p_err) {
         typename L::State s;
         const uint32_t ep = h->episodes[e];
         if (h->min_err > 0) reset_lattice_n<D>(s, h->seed, (uint32_t)(h->first_env + e), ep, h->min_err);
-        else reset_lattice<D>(s, h->seed, (uint32_t)(h->first_env + e), ep, p_err ? p_err[e] : h->p_default);
+        else reset_lattice<D>(s, h->seed, (uint32_t)(h->first_env + e), ep, p_err ? p_err[e] : h->sched.p_default);
         if (!(s.v.any() || s.p.any())) err |= ERR_RESET_ROUNDS;
         store_state<D>(h, e, s);
         h->episodes[e] = ep + 1;
@@ -113,33 +101,12 @@ int reset_all(tq_env* h, const double* p_err) {
     return TQ_OK;
 }
 
-struct Block {     // SoA sections of a packed transition block (include/toricenv.h; csrc/kernels.hpp:206-225)
-    uint64_t *pv, *pp, *nv, *np;
-    uint32_t* action; float* reward; float* priority; uint8_t* terminal;
-    int64_t cap;
-};
-Block block_view(void* base, int W, int64_t cap) {
-    Block b;
-    char* p = (char*)base;
-    b.cap = cap;
-    b.pv = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.pp = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.nv = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.np = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.action = (uint32_t*)p; p += align8(4 * cap);
-    b.reward = (float*)p; p += align8(4 * cap);
-    b.priority = (float*)p; p += align8(4 * cap);
-    b.terminal = (uint8_t*)p;
-    return b;
-}
-
-// tq_actor_step: k_actor_step (csrc/kernels.hpp:333-433), one lattice after the other
+// tq_actor_step: k_actor_step, one lattice after the other
 template <int D>
 int actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float* rewards, uint8_t* terminals, void* block,
                int64_t block_cap, int64_t slot_base) {
     using L = Lat<D>;
-    constexpr int W = L::W, GS = L::GS, DD = L::DD;
-    const Block blk = block ? block_view(block, W, block_cap) : Block{};
+    const BlockView blk = block ? block_view(block, L::W, block_cap) : BlockView{};
     int err = 0;
 #pragma omp parallel for schedule(static) reduction(| : err)
     for (int64_t e = 0; e < h->n; ++e) {
@@ -150,67 +117,29 @@ int actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float* r
         bool ok;
         if (actions) {
             layer = actions[4 * e]; row = actions[4 * e + 1]; col = actions[4 * e + 2]; op = actions[4 * e + 3];
-            ok = ((unsigned)layer < 2u) & ((unsigned)row < (unsigned)D) & ((unsigned)col < (unsigned)D) & ((unsigned)(op - 1) < 3u);
-            if (!ok && op != 0) err |= ERR_ACTION;
-        } else {                                               // non-greedy branch of _selectActionBatch_prime (numba/util_actor.py:97-98)
-            typename L::B e0, e1;
-            L::hit_masks(s.v, s.p, e0, e1);
-            const int n = e0.popc() + e1.popc();
-            ok = n > 0;
-            layer = row = col = op = 0;
-            if (ok) {
-                const U4 w = draw(h->seed, env, ep, st, DOMAIN_SEL, 0);
-                const int hh = kth_hit<D>(e0, e1, (int)mulhi32(w.y, (uint32_t)n));
-                layer = hh >= DD;
-                const int rem = hh - layer * DD;
-                row = rem / D; col = rem - row * D;
-                op = 1 + (int)mulhi32(w.z, 3);
-            }
+            ok = action_ok<D>(layer, row, col, op);
+            if (!ok && !action_noop(op)) err |= ERR_ACTION;
+        } else {
+            ok = explore_action<D>(s.v, s.p, h->seed, env, ep, st, layer, row, col, op);
         }
         if (actions_out) { actions_out[4 * e] = layer; actions_out[4 * e + 1] = row; actions_out[4 * e + 2] = col; actions_out[4 * e + 3] = op; }
         const typename L::B v0 = s.v, p0 = s.p;
-        const int before = v0.popc() + p0.popc();
-        if (ok) L::apply(s, layer, row, col, op);
-        L::syndrome(s);
-        const int after = s.v.popc() + s.p.popc();
-        const int terminal = after == 0;
-        const float reward = terminal ? (float)h->terminal_reward : (float)(before - after);
+        float reward;
+        const int terminal = step_lattice<D>(s, ok, layer, row, col, op, (float)h->terminal_reward, reward);
         st += 1;
         if (rewards) rewards[e] = reward;
         if (terminals) terminals[e] = (uint8_t)terminal;
-        if (block) {                                           // every slot is written, every step (csrc/kernels.hpp:244-283)
-            const int64_t slot = slot_base + e;
-            typename L::B a, c;
-            if (ok) {
-                L::perspective(v0, p0, layer, row, col, a, c);
-                for (int k = 0; k < W; ++k) { blk.pv[(int64_t)k * blk.cap + slot] = a.w[k]; blk.pp[(int64_t)k * blk.cap + slot] = c.w[k]; }
-                L::perspective(s.v, s.p, layer, row, col, a, c);
-                for (int k = 0; k < W; ++k) { blk.nv[(int64_t)k * blk.cap + slot] = a.w[k]; blk.np[(int64_t)k * blk.cap + slot] = c.w[k]; }
-                blk.action[slot] = (uint32_t)layer | ((uint32_t)GS << 8) | ((uint32_t)GS << 16) | ((uint32_t)op << 24);
-                blk.reward[slot] = reward;
-                blk.terminal[slot] = (uint8_t)terminal;
-            } else {
-                for (int k = 0; k < W; ++k) {
-                    blk.pv[(int64_t)k * blk.cap + slot] = 0; blk.pp[(int64_t)k * blk.cap + slot] = 0;
-                    blk.nv[(int64_t)k * blk.cap + slot] = 0; blk.np[(int64_t)k * blk.cap + slot] = 0;
-                }
-                blk.action[slot] = 0u; blk.reward[slot] = 0.f; blk.terminal[slot] = 0;
-            }
+        if (block) {                                           // every slot is written, every step
+            if (ok) write_transition<D>(blk, slot_base + e, v0, p0, s.v, s.p, layer, row, col, op, reward, terminal, true);
+            else write_empty_slot<D>(blk, slot_base + e);
         }
-        // reset policy of the caller (Actor_mp.py:171-183)
+        // reset policy of the caller (Actor_mp.py:171-183): a plain call where the kernel has the whole wave serve the lane
         if (terminal || st > (uint32_t)h->max_steps) {
-            double p = h->p_default;
-            if (h->strategy != 0) {
-                double roof = h->p_roof[e] + h->p_delta;
-                roof = roof < h->p_final ? roof : h->p_final;
+            double p = h->sched.p_default;
+            if (h->sched.strategy != 0) {
+                double roof = h->p_roof[e];
+                p = scheduled_p_error(h->sched, roof, h->seed, env, ep);
                 h->p_roof[e] = roof;
-                p = roof;
-                if (h->strategy == 2) {
-                    const U4 w = draw(h->seed, env, ep, 0, DOMAIN_PERR, 0);
-                    const double span = roof - h->p_start;
-                    const double t = span * u01(w.x);
-                    p = h->p_start + t;
-                }
             }
             typename L::State fresh;
             if (h->min_err > 0) reset_lattice_n<D>(fresh, h->seed, env, ep, h->min_err);
@@ -308,8 +237,8 @@ int tq_create(tq_env** out, int n_envs, int d, int device, uint64_t seed, int64_
     if (!h) return fail(TQ_E_HIP, "out of host memory");
     h->n = n_envs; h->d = d; h->w = (d * d + 63) / 64;
     h->seed = seed; h->first_env = first_env_id;
-    h->p_default = 0.1; h->terminal_reward = 100.0; h->max_steps = 75; h->min_err = 0;
-    h->strategy = 0; h->p_start = h->p_final = 0.1; h->p_delta = 0.0;
+    h->sched = PerrSchedule{TQ_PERR_FIXED, 0.1, 0.1, 0.1, 0.0};
+    h->terminal_reward = 100.0; h->max_steps = 75; h->min_err = 0;
     h->planes.assign((size_t)6 * h->w * n_envs, 0);
     h->episodes.assign(n_envs, 0); h->steps.assign(n_envs, 0); h->counts.assign(n_envs, 0);
     h->p_roof.assign(n_envs, 0.0);
@@ -327,13 +256,13 @@ int tq_set_params(tq_env* h, double p_error_default, double terminal_reward, int
     if (!((p_error_default > 0.0 || (p_unused && p_error_default == 0.0)) && p_error_default <= 1.0))
         return fail(TQ_E_INVALID, "p_error must be in (0,1] (0 is accepted only with min_qubit_errors > 0)");
     if (max_steps_per_episode < 1) return fail(TQ_E_INVALID, "max_steps_per_episode must be >= 1");
-    h->p_default = p_error_default; h->terminal_reward = terminal_reward; h->max_steps = max_steps_per_episode;
+    h->sched.p_default = p_error_default; h->terminal_reward = terminal_reward; h->max_steps = max_steps_per_episode;
     return TQ_OK;
 }
 int tq_set_min_qubit_errors(tq_env* h, int n_errors) {
     if (!h) return fail(TQ_E_INVALID, "NULL handle");
     if (n_errors < 0 || n_errors > 2 * h->d * h->d) return fail(TQ_E_INVALID, "min_qubit_errors must be in [0, 2*d*d]");
-    if (n_errors == 0 && !(h->p_default > 0.0))
+    if (n_errors == 0 && !(h->sched.p_default > 0.0))
         return fail(TQ_E_INVALID, "min_qubit_errors = 0 selects the depolarizing sampler, which needs p_error in (0,1]");
     h->min_err = n_errors;
     return TQ_OK;
@@ -343,7 +272,7 @@ int tq_set_perror_schedule(tq_env* h, int strategy, double p_start, double p_fin
     if (strategy < TQ_PERR_FIXED || strategy > TQ_PERR_RANDOM) return fail(TQ_E_INVALID, "unknown p_error strategy %d", strategy);
     if (!(p_start > 0.0 && p_start <= 1.0 && p_final > 0.0 && p_final <= 1.0 && p_delta >= 0.0))
         return fail(TQ_E_INVALID, "p_error schedule needs 0 < p_start, p_final <= 1 and p_delta >= 0");
-    h->strategy = strategy; h->p_start = p_start; h->p_final = p_final; h->p_delta = p_delta;
+    h->sched.strategy = strategy; h->sched.p_start = p_start; h->sched.p_final = p_final; h->sched.p_delta = p_delta;
     for (auto& r : h->p_roof) r = p_start;
     return TQ_OK;
 }
@@ -404,8 +333,7 @@ int tq_persp_write(tq_env* h, const int64_t* offsets, void* out, int32_t* positi
 
 int64_t tq_transition_block_bytes(int d, int64_t cap) {
     if (d < 3 || d > 21 || !(d & 1) || cap <= 0) return -1;
-    const int W = (d * d + 63) / 64;
-    return 4 * 8 * (int64_t)W * cap + 3 * align8(4 * cap) + align8(cap);
+    return block_bytes((d * d + 63) / 64, cap);
 }
 
 int tq_actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float* rewards, uint8_t* terminals, void* block,

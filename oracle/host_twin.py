@@ -20,7 +20,8 @@ STRATEGY = {"fixed": 0, "linear": 1, "random": 2}
 
 
 def build(force=False):
-    srcs = [os.path.join(_HERE, "host_twin.cpp"), os.path.join(_HERE, "..", "toric-rl-decoder_amd", "csrc", "lattice.hpp"),
+    csrc = os.path.join(_HERE, "..", "toric-rl-decoder_amd", "csrc")
+    srcs = [os.path.join(_HERE, "host_twin.cpp"), os.path.join(csrc, "lattice.hpp"), os.path.join(csrc, "env_step.hpp"),
             os.path.join(_HERE, "..", "include", "toricenv.h")]
     if force or not os.path.exists(_PATH) or os.path.getmtime(_PATH) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-B", "libtoricenv_host_twin.so"], stdout=subprocess.DEVNULL,

@@ -20,12 +20,9 @@
 #include <hip/hip_fp16.h>
 #include <stdint.h>
 
-#include "lattice.hpp"
+#include "env_step.hpp"
 
 namespace tq {
-
-enum { PL_X0 = 0, PL_X1 = 1, PL_Z0 = 2, PL_Z1 = 3, PL_V = 4, PL_P = 5 };
-enum { ERR_ACTION = 1, ERR_CAPACITY = 2, ERR_RESET_DUP = 4, ERR_RESET_ROUNDS = 8, ERR_INDEX = 16 };
 
 template <int W>
 __device__ __forceinline__ Bits<W> load_plane(const uint64_t* __restrict__ planes, int plane, int64_t N, int64_t e) {
@@ -61,51 +58,6 @@ __device__ __forceinline__ void store_state(uint64_t* __restrict__ planes, int64
     store_plane<W>(planes, PL_V, N, e, s.v);
     store_plane<W>(planes, PL_P, N, e, s.p);
 }
-
-// Position of the k-th set bit (k < popc) of the concatenated hit mask [E0 | E1] as a flat
-// qubit index layer*DD + row*D + col -- the k-th entry of the reference's positions list.
-template <int D>
-__device__ __forceinline__ int kth_hit(const typename Lat<D>::B& e0, const typename Lat<D>::B& e1, int k) {
-    constexpr int W = Lat<D>::W;
-    constexpr int DD = Lat<D>::DD;
-    int base = 0;
-    uint64_t word = 0;
-    bool found = false;
-#pragma unroll
-    for (int l = 0; l < 2; ++l) {
-#pragma unroll
-        for (int j = 0; j < W; ++j) {
-            const uint64_t wv = l ? e1.w[j] : e0.w[j];
-            const int c = popc64(wv);
-            const bool here = !found && k < c;
-            word = here ? wv : word;
-            base = here ? l * DD + 64 * j : base;
-            k = (found || here) ? k : k - c;
-            found = found || here;
-        }
-    }
-    // position of the k-th set bit of `word` (k < popc(word)): binary search on popcounts, six steps,
-    // no data-dependent loop (a wave pays for its slowest lane)
-    uint32_t w32 = (uint32_t)word;
-    int posn = 0;
-    {
-        const int c = __popc(w32);
-        const bool up = k >= c;
-        k = up ? k - c : k; posn = up ? 32 : 0; w32 = up ? (uint32_t)(word >> 32) : w32;
-    }
-#pragma unroll
-    for (int s = 16; s >= 1; s >>= 1) {
-        const int c = __popc(w32 & ((1u << s) - 1u));
-        const bool up = k >= c;
-        k = up ? k - c : k; posn += up ? s : 0; w32 = up ? (w32 >> s) : w32;
-    }
-    return base + posn;
-}
-
-struct PerrSchedule {
-    int strategy;          // TQ_PERR_*
-    double p_default, p_start, p_final, p_delta;
-};
 
 // First pass of the exclusive scan, folded into the kernels that produce the hit counts: every
 // 256-thread block of an all-lattice kernel leaves the sum of its 256 counts in part256[blockIdx.x].
@@ -161,16 +113,6 @@ __global__ __launch_bounds__(256) void k_reset(uint64_t* __restrict__ planes, ui
     if (part256) block_count_partial(cnt, part256);          // all-lattice mode only (uniform branch)
 }
 
-// validated decode of action = [layer,row,col,op]
-template <int D>
-__device__ __forceinline__ bool action_ok(int layer, int row, int col, int op) {
-    return ((unsigned)layer < 2u) & ((unsigned)row < (unsigned)D) & ((unsigned)col < (unsigned)D) &
-           ((unsigned)(op - 1) < 3u);
-}
-// op == 0 is "no action" (what tq_select_action emits for a lattice without defects): the step is
-// counted, nothing changes, and no error is latched.
-__device__ __forceinline__ bool action_noop(int op) { return op == 0; }
-
 // ------------------------------------------------------------------ step (EnvSet.step)
 template <int D>
 __global__ __launch_bounds__(256) void k_step(uint64_t* __restrict__ planes, uint64_t* __restrict__ prev,
@@ -187,99 +129,18 @@ __global__ __launch_bounds__(256) void k_step(uint64_t* __restrict__ planes, uin
         const int4 a = reinterpret_cast<const int4*>(actions)[e];
         store_plane<W>(prev, 0, N, e, s.v);
         store_plane<W>(prev, 1, N, e, s.p);
-        const int before = s.v.popc() + s.p.popc();
-        if (action_ok<D>(a.x, a.y, a.z, a.w)) L::apply(s, a.x, a.y, a.z, a.w);
-        else if (!action_noop(a.w)) atomicOr(err, ERR_ACTION);
-        L::syndrome(s);
-        const int after = s.v.popc() + s.p.popc();
+        const bool ok = action_ok<D>(a.x, a.y, a.z, a.w);
+        if (!ok && !action_noop(a.w)) atomicOr(err, ERR_ACTION);
+        float reward;
+        const int terminal = step_lattice<D>(s, ok, a.x, a.y, a.z, a.w, terminal_reward, reward);
         store_state<D>(planes, N, e, s);
-        if (rewards) rewards[e] = after == 0 ? terminal_reward : (float)(before - after);
-        if (terminals) terminals[e] = after == 0;
+        if (rewards) rewards[e] = reward;
+        if (terminals) terminals[e] = (uint8_t)terminal;
         steps[e] += 1;
         cnt = L::persp_count(s.v, s.p);
         counts[e] = cnt;
     }
     block_count_partial(cnt, part256);
-}
-
-// ------------------------------------------------------------------ packed transition block
-struct BlockView {     // SoA sections of a packed transition block (see include/toricenv.h)
-    uint64_t* pv; uint64_t* pp; uint64_t* nv; uint64_t* np;
-    uint32_t* action; float* reward; float* priority; uint8_t* terminal;
-    int64_t cap;
-};
-__host__ __device__ inline int64_t align8(int64_t x) { return (x + 7) & ~(int64_t)7; }
-__host__ __device__ inline BlockView block_view(void* base, int W, int64_t cap) {
-    BlockView b;
-    char* p = (char*)base;
-    b.cap = cap;
-    b.pv = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.pp = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.nv = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.np = (uint64_t*)p; p += 8 * (int64_t)W * cap;
-    b.action = (uint32_t*)p; p += align8(4 * cap);
-    b.reward = (float*)p; p += align8(4 * cap);
-    b.priority = (float*)p; p += align8(4 * cap);
-    b.terminal = (uint8_t*)p;
-    return b;
-}
-__host__ __device__ inline int64_t block_bytes(int W, int64_t cap) {
-    return 4 * 8 * (int64_t)W * cap + 3 * align8(4 * cap) + align8(cap);
-}
-
-// The four checks of the acted qubit in ITS OWN centred frame -- v[gs,gs], v[gs+1,gs], p[gs,gs], p[gs,gs-1], for
-// either layer (centred-frame property) -- so the perspective of the post-step syndrome is the
-// perspective of the pre-step syndrome with these bits flipped: Z component -> the two vertices, X component
-// -> the two plaquettes.  (perspective() is linear over GF(2).)
-template <int D>
-__device__ __forceinline__ void centred_flip(int op, typename Lat<D>::B& dv, typename Lat<D>::B& dp) {
-    using L = Lat<D>;
-    constexpr int GS = L::GS;
-    dv = L::B::zero(); dp = L::B::zero();
-    const int fx = (op == 1) | (op == 2), fz = (op >> 1) & 1;
-    dv.flip(GS * D + GS, fz); dv.flip((GS + 1) * D + GS, fz);
-    dp.flip(GS * D + GS, fx); dp.flip(GS * D + GS - 1, fx);
-}
-
-template <int D>
-__device__ __forceinline__ void write_transition(const BlockView& b, int64_t slot, const typename Lat<D>::B& v0,
-                                                 const typename Lat<D>::B& p0, const typename Lat<D>::B& v1,
-                                                 const typename Lat<D>::B& p1, int layer, int row, int col, int op,
-                                                 float reward, int terminal, bool stepped = false) {
-    using L = Lat<D>;
-    constexpr int W = L::W;
-    typename L::B a, c;
-    L::perspective(v0, p0, layer, row, col, a, c);
-#pragma unroll
-    for (int k = 0; k < W; ++k) { b.pv[(int64_t)k * b.cap + slot] = a.w[k]; b.pp[(int64_t)k * b.cap + slot] = c.w[k]; }
-    if (stepped) {                                            // (v1,p1) = (v0,p0) after `op` on this very qubit
-        typename L::B dv, dp;
-        centred_flip<D>(op, dv, dp);
-        a = a ^ dv; c = c ^ dp;
-    } else {
-        L::perspective(v1, p1, layer, row, col, a, c);
-    }
-#pragma unroll
-    for (int k = 0; k < W; ++k) { b.nv[(int64_t)k * b.cap + slot] = a.w[k]; b.np[(int64_t)k * b.cap + slot] = c.w[k]; }
-    // action rewritten to the centred frame (util_actor.py:256,261)
-    b.action[slot] = (uint32_t)layer | ((uint32_t)L::GS << 8) | ((uint32_t)L::GS << 16) | ((uint32_t)op << 24);
-    b.reward[slot] = reward;
-    b.terminal[slot] = (uint8_t)terminal;
-}
-
-// A slot without a transition (no-op or rejected action): action word 0 (op = 0 marks the slot
-// invalid for tq_transition_unpack / wire.decode), everything else zero -- never stale data.
-template <int D>
-__device__ __forceinline__ void write_empty_slot(const BlockView& b, int64_t slot) {
-    constexpr int W = Lat<D>::W;
-#pragma unroll
-    for (int k = 0; k < W; ++k) {
-        b.pv[(int64_t)k * b.cap + slot] = 0; b.pp[(int64_t)k * b.cap + slot] = 0;
-        b.nv[(int64_t)k * b.cap + slot] = 0; b.np[(int64_t)k * b.cap + slot] = 0;
-    }
-    b.action[slot] = 0u;
-    b.reward[slot] = 0.f;
-    b.terminal[slot] = 0;
 }
 
 // generateTransitionParallel for the last tq_step, into a packed block
@@ -361,29 +222,12 @@ __global__ __launch_bounds__(256) void k_actor_step(const uint64_t* __restrict__
         ok = action_ok<D>(layer, row, col, op);
         if (!ok && !action_noop(op) && valid) atomicOr(err, ERR_ACTION);
     } else {
-        // non-greedy branch of _selectActionBatch_prime (numba/util_actor.py:97-98)
-        typename L::B e0, e1;
-        L::hit_masks(s.v, s.p, e0, e1);
-        const int n = e0.popc() + e1.popc();
-        ok = n > 0;
-        layer = row = col = op = 0;
-        if (ok) {
-            const U4 w = draw(seed, env, ep, st, DOMAIN_SEL, 0);
-            const int h = kth_hit<D>(e0, e1, (int)mulhi32(w.y, (uint32_t)n));
-            layer = h >= L::DD;
-            const int rem = h - layer * L::DD;
-            row = rem / D; col = rem - row * D;
-            op = 1 + (int)mulhi32(w.z, 3);
-        }
+        ok = explore_action<D>(s.v, s.p, seed, env, ep, st, layer, row, col, op);
     }
     if (actions_out && valid) reinterpret_cast<int4*>(actions_out)[e] = make_int4(layer, row, col, op);
     const typename L::B v0 = s.v, p0 = s.p;
-    const int before = v0.popc() + p0.popc();
-    if (ok) L::apply(s, layer, row, col, op);
-    L::syndrome(s);
-    const int after = s.v.popc() + s.p.popc();
-    const int terminal = after == 0;
-    const float reward = terminal ? terminal_reward : (float)(before - after);
+    float reward;
+    const int terminal = step_lattice<D>(s, ok, layer, row, col, op, terminal_reward, reward);
     st += 1;
     if (rewards && valid) rewards[e] = reward;
     if (terminals && valid) terminals[e] = (uint8_t)terminal;
@@ -396,19 +240,10 @@ __global__ __launch_bounds__(256) void k_actor_step(const uint64_t* __restrict__
     // instead of a 98-iteration loop in one lane while 63 wait).
     const bool need_reset = valid && (terminal || st > (uint32_t)max_steps);
     double p = sched.p_default;
-    if (need_reset) {
-        if (sched.strategy != 0) {
-            double roof = p_roof[e] + sched.p_delta;
-            roof = roof < sched.p_final ? roof : sched.p_final;
-            p_roof[e] = roof;
-            p = roof;
-            if (sched.strategy == 2) {
-                const U4 w = draw(seed, env, ep, 0, DOMAIN_PERR, 0);
-                const double span = roof - sched.p_start;
-                const double t = span * u01(w.x);
-                p = sched.p_start + t;
-            }
-        }
+    if (need_reset && sched.strategy != 0) {
+        double roof = p_roof[e];
+        p = scheduled_p_error(sched, roof, seed, env, ep);
+        p_roof[e] = roof;
     }
     uint64_t pending = __ballot(need_reset);
     while (pending) {                                        // wave-uniform

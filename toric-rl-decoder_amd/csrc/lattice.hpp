@@ -35,6 +35,13 @@ TQ_HD int popc64(uint64_t x) {
     return __builtin_popcountll(x);
 #endif
 }
+TQ_HD int popc32(uint32_t x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __popc(x);
+#else
+    return __builtin_popcount(x);
+#endif
+}
 
 template <int W>
 struct Bits {
