@@ -40,6 +40,10 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
+int bad_size(int d) { return fail(TQ_E_INVALID, "unsupported lattice size d=%d (odd 3..21)", d); }
+// f(D) with the handle's lattice size as a compile-time constant, so that f names a template<D()> above
+template <class F>
+int by_size(int d, F&& f) { return dispatch_size(d, f, bad_size); }
 }  // namespace
 
 struct tq_env {
@@ -191,7 +195,7 @@ int persp_write(tq_env* h, const int64_t* offsets, OutT* out, int32_t* positions
 }
 
 template <int D>
-void get_state(const tq_env* h, uint8_t* out, bool qubits) {
+int get_state(const tq_env* h, uint8_t* out, bool qubits) {
     using L = Lat<D>;
     constexpr int DD = L::DD, NQ = L::NQ;
 #pragma omp parallel for schedule(static)
@@ -203,22 +207,8 @@ void get_state(const tq_env* h, uint8_t* out, bool qubits) {
             else { o[c] = (uint8_t)s.v.get(c); o[DD + c] = (uint8_t)s.p.get(c); }
         }
     }
+    return TQ_OK;
 }
-
-#define DISPATCH_D(d, CALL)          \
-    switch (d) {                     \
-        case 3: CALL(3); break;      \
-        case 5: CALL(5); break;      \
-        case 7: CALL(7); break;      \
-        case 9: CALL(9); break;      \
-        case 11: CALL(11); break;    \
-        case 13: CALL(13); break;    \
-        case 15: CALL(15); break;    \
-        case 17: CALL(17); break;    \
-        case 19: CALL(19); break;    \
-        case 21: CALL(21); break;    \
-        default: return fail(TQ_E_INVALID, "unsupported lattice size d=%d (odd 3..21)", d); \
-    }
 }  // namespace
 
 extern "C" {
@@ -231,7 +221,7 @@ int tq_create(tq_env** out, int n_envs, int d, int device, uint64_t seed, int64_
     *out = nullptr;
     if (device != -1) return fail(TQ_E_INVALID, "this is the host twin of the ABI: device must be -1 (got %d)", device);
     if (n_envs <= 0) return fail(TQ_E_INVALID, "n_envs must be > 0 (got %d)", n_envs);
-    if (d < 3 || d > 21 || !(d & 1)) return fail(TQ_E_INVALID, "unsupported lattice size d=%d (odd 3..21)", d);
+    if (!size_ok(d)) return bad_size(d);
     if (first_env_id < 0 || first_env_id + n_envs > 0xFFFFFFFFll) return fail(TQ_E_INVALID, "global env ids must fit in 32 bits");
     tq_env* h = new (std::nothrow) tq_env();
     if (!h) return fail(TQ_E_HIP, "out of host memory");
@@ -279,24 +269,15 @@ int tq_set_perror_schedule(tq_env* h, int strategy, double p_start, double p_fin
 
 int tq_reset_all(tq_env* h, const double* p_err, void*) {
     if (!h) return fail(TQ_E_INVALID, "NULL handle");
-#define CALL(D) return reset_all<D>(h, p_err)
-    DISPATCH_D(h->d, CALL)
-#undef CALL
-    return TQ_OK;
+    return by_size(h->d, [&](auto D) { return reset_all<D()>(h, p_err); });
 }
 int tq_get_state(tq_env* h, uint8_t* out, void*) {
     if (!h || !out) return fail(TQ_E_INVALID, "NULL handle / out");
-#define CALL(D) get_state<D>(h, out, false)
-    DISPATCH_D(h->d, CALL)
-#undef CALL
-    return TQ_OK;
+    return by_size(h->d, [&](auto D) { return get_state<D()>(h, out, false); });
 }
 int tq_get_qubits(tq_env* h, uint8_t* out, void*) {
     if (!h || !out) return fail(TQ_E_INVALID, "NULL handle / out");
-#define CALL(D) get_state<D>(h, out, true)
-    DISPATCH_D(h->d, CALL)
-#undef CALL
-    return TQ_OK;
+    return by_size(h->d, [&](auto D) { return get_state<D()>(h, out, true); });
 }
 int tq_get_counters(tq_env* h, uint32_t* episodes, uint32_t* steps, void*) {
     if (!h) return fail(TQ_E_INVALID, "NULL handle");
@@ -319,20 +300,15 @@ int tq_persp_count(tq_env* h, int32_t* counts, int64_t* offsets, void*) {
 int tq_persp_write(tq_env* h, const int64_t* offsets, void* out, int32_t* positions, int64_t capacity, int dtype, void*) {
     if (!h || !offsets || !out) return fail(TQ_E_INVALID, "NULL handle / offsets / out");
     if (capacity < 0) return fail(TQ_E_INVALID, "negative capacity");
-    if (dtype == TQ_F32) {
-#define CALL(D) return persp_write<D, float>(h, offsets, (float*)out, positions, capacity)
-        DISPATCH_D(h->d, CALL)
-#undef CALL
-    } else if (dtype == TQ_U8) {
-#define CALL(D) return persp_write<D, uint8_t>(h, offsets, (uint8_t*)out, positions, capacity)
-        DISPATCH_D(h->d, CALL)
-#undef CALL
-    }
+    if (dtype == TQ_F32)
+        return by_size(h->d, [&](auto D) { return persp_write<D(), float>(h, offsets, (float*)out, positions, capacity); });
+    if (dtype == TQ_U8)
+        return by_size(h->d, [&](auto D) { return persp_write<D(), uint8_t>(h, offsets, (uint8_t*)out, positions, capacity); });
     return fail(TQ_E_INVALID, "the host twin writes f32 and u8 stacks only (dtype %d)", dtype);
 }
 
 int64_t tq_transition_block_bytes(int d, int64_t cap) {
-    if (d < 3 || d > 21 || !(d & 1) || cap <= 0) return -1;
+    if (!size_ok(d) || cap <= 0) return -1;
     return block_bytes((d * d + 63) / 64, cap);
 }
 
@@ -340,10 +316,9 @@ int tq_actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float
                   int64_t block_cap, int64_t slot_base, void*) {
     if (!h) return fail(TQ_E_INVALID, "NULL handle");
     if (block && (slot_base < 0 || slot_base + h->n > block_cap)) return fail(TQ_E_INVALID, "slots outside the block");
-#define CALL(D) return actor_step<D>(h, actions, actions_out, rewards, terminals, block, block_cap, slot_base)
-    DISPATCH_D(h->d, CALL)
-#undef CALL
-    return TQ_OK;
+    return by_size(h->d, [&](auto D) {
+        return actor_step<D()>(h, actions, actions_out, rewards, terminals, block, block_cap, slot_base);
+    });
 }
 
 int tq_check(tq_env* h, void*) {

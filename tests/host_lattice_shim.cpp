@@ -118,22 +118,6 @@ static void t_step(int n, uint8_t* q, const int32_t* act, uint8_t* st, int32_t* 
     }
 }
 
-#define DISPATCH(d, CALL)                  \
-    switch (d) {                           \
-        case 3: CALL(3); break;            \
-        case 5: CALL(5); break;            \
-        case 7: CALL(7); break;            \
-        case 9: CALL(9); break;            \
-        case 11: CALL(11); break;          \
-        case 13: CALL(13); break;          \
-        case 15: CALL(15); break;          \
-        case 17: CALL(17); break;          \
-        case 19: CALL(19); break;          \
-        case 21: CALL(21); break;          \
-        default: return -1;                \
-    }                                      \
-    return 0;
-
 // The perspective stack of each lattice through the bitstream algebra the stack-write kernel uses
 // (PStream): rotated planes, row-rolled table, masked column rolls, emit into the stream, window
 // reads back -- every lane's work done serially here.  out: u8 (P,2,d,d) at offsets[e]*NQ.
@@ -173,48 +157,38 @@ static void t_stream_stack(int n, const uint8_t* st, const int64_t* offsets, uin
     }
 }
 
+// f(D) with the lattice size as a compile-time constant; -1 for a size the library does not have
+template <class F>
+static int by_size(int d, F&& f) {
+    return dispatch_size(d, [&](auto D) { f(D); return 0; }, [](int) { return -1; });
+}
+
 extern "C" {
 int shim_stream_stack(int d, int n, const uint8_t* st, const int64_t* offsets, uint8_t* out) {
-#define C_(D) t_stream_stack<D>(n, st, offsets, out)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_stream_stack<D()>(n, st, offsets, out); });
 }
 int shim_syndrome(int d, int n, const uint8_t* q, uint8_t* st) {
-#define C_(D) t_syndrome<D>(n, q, st)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_syndrome<D()>(n, q, st); });
 }
 int shim_counts(int d, int n, const uint8_t* st, int32_t* counts, uint8_t* masks) {
-#define C_(D) t_counts<D>(n, st, counts, masks)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_counts<D()>(n, st, counts, masks); });
 }
 int shim_lut(int d, int32_t* lut) {
-#define C_(D) t_lut<D>(lut)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_lut<D()>(lut); });
 }
 int shim_perspective(int d, int n, const uint8_t* st, const int32_t* act, uint8_t* out) {
-#define C_(D) t_perspective<D>(n, st, act, out)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_perspective<D()>(n, st, act, out); });
 }
 int shim_reset(int d, int n, uint64_t seed, int64_t first_env, const uint32_t* episodes, const double* p,
                uint8_t* q, uint8_t* st, int32_t* rounds) {
-#define C_(D) t_reset<D>(n, seed, first_env, episodes, p, q, st, rounds)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_reset<D()>(n, seed, first_env, episodes, p, q, st, rounds); });
 }
 int shim_reset_n(int d, int n, uint64_t seed, int64_t first_env, const uint32_t* episodes, int n_err, uint8_t* q,
                  uint8_t* st) {
-#define C_(D) t_reset_n<D>(n, seed, first_env, episodes, n_err, q, st)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_reset_n<D()>(n, seed, first_env, episodes, n_err, q, st); });
 }
 int shim_step(int d, int n, uint8_t* q, const int32_t* act, uint8_t* st, int32_t* ground) {
-#define C_(D) t_step<D>(n, q, act, st, ground)
-    DISPATCH(d, C_)
-#undef C_
+    return by_size(d, [&](auto D) { t_step<D()>(n, q, act, st, ground); });
 }
 void shim_philox(const uint32_t* ctr, const uint32_t* key, uint32_t* out) {
     U4 r = philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);

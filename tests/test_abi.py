@@ -47,6 +47,9 @@ def test_version_and_block_layout(lib):
             assert lib.tq_transition_block_bytes(d, cap) == wire.block_bytes(d, cap)
     assert lib.tq_transition_block_bytes(4, 8) == -1
     assert lib.tq_transition_block_bytes(7, -1) == -1
+    # T.SUPPORTED_SIZES (Python) and the library's own list of sizes (csrc/lattice.hpp) are the same set
+    for d in range(0, 40):
+        assert (lib.tq_transition_block_bytes(d, 1) != -1) == (d in T.SUPPORTED_SIZES), d
 
 
 def test_errors_are_codes_not_aborts(lib):

@@ -4,8 +4,11 @@ There is no CPU fallback: if the library is missing or no HIP device is usable t
 functions raise -- a GPU box must never pass silently on some other path.
 """
 import ctypes as C
+import glob
 import os
 import subprocess
+
+import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtoricenv.so")
@@ -83,8 +86,8 @@ class ToricEnvError(RuntimeError):
 
 def build(force=False, verbose=False):
     """Compile libtoricenv.so for gfx950 with hipcc (cross-compiles without a GPU)."""
-    srcs = [os.path.join(CSRC, f) for f in ("toricenv.hip", "kernels.hpp", "env_step.hpp", "stream_write.hpp", "lattice.hpp", "replay.hpp", "Makefile")]
-    srcs.append(os.path.join(_HERE, "..", "include", "toricenv.h"))
+    srcs = glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))
+    srcs += [os.path.join(CSRC, "Makefile"), os.path.join(_HERE, "..", "include", "toricenv.h")]
     stale = (not os.path.exists(LIB_PATH)) or any(os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
     if force or stale:
         cmd = ["make", "-C", CSRC] + (["-B"] if force else [])
@@ -108,6 +111,14 @@ def load():
             fn.argtypes = args
         _lib = lib
     return _lib
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _ptr(t):
+    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def check(rc):

@@ -19,6 +19,9 @@
 #pragma once
 #include <stdint.h>
 
+#include <type_traits>
+#include <utility>
+
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define TQ_HD __host__ __device__ __forceinline__
@@ -412,5 +415,26 @@ TQ_HD int reset_lattice_n(typename Lat<D>::State& s, uint64_t seed, uint32_t env
     }
     return r;
 }
+
+// ---- the supported lattice sizes, said once (host code: the library's C-ABI and the CPU shells dispatch on them)
+constexpr int SIZES[] = {3, 5, 7, 9, 11, 13, 15, 17, 19, 21};
+constexpr int N_SIZES = sizeof(SIZES) / sizeof(SIZES[0]);
+
+inline int size_slot(int d) {                  // position of d in SIZES, -1 for an unsupported size
+    for (int i = 0; i < N_SIZES; ++i) if (SIZES[i] == d) return i;
+    return -1;
+}
+inline bool size_ok(int d) { return size_slot(d) >= 0; }
+
+template <class F, class Bad, size_t... I>
+auto dispatch_size_(int d, F& f, Bad& bad, std::index_sequence<I...>) {
+    decltype(bad(d)) r{};
+    const bool hit = (... || (d == SIZES[I] && (r = f(std::integral_constant<int, SIZES[I]>{}), true)));
+    return hit ? r : bad(d);
+}
+// f(std::integral_constant<int, D>{}) for the supported size D == d, so that f can name Lat<D()> or a kernel<D()>;
+// bad(d), which is not called otherwise, for any other d.  Returns what the one that was called returns.
+template <class F, class Bad>
+auto dispatch_size(int d, F&& f, Bad&& bad) { return dispatch_size_(d, f, bad, std::make_index_sequence<N_SIZES>{}); }
 
 }  // namespace tq

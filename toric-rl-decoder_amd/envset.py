@@ -21,19 +21,11 @@ import numpy as np
 import torch
 
 from . import _lib, wire
-from ._lib import TQ_BF16, TQ_F16, TQ_F32, TQ_U8, check
+from ._lib import TQ_BF16, TQ_F16, TQ_F32, TQ_U8, _ptr, _stream, check
 
 _DTYPES = {torch.float32: TQ_F32, torch.float16: TQ_F16, torch.bfloat16: TQ_BF16, torch.uint8: TQ_U8}
 _STRATEGY = {None: 0, "fixed": 0, "linear": 1, "random": 2}
 SUPPORTED_SIZES = (3, 5, 7, 9, 11, 13, 15, 17, 19, 21)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def _require_gpu(device):

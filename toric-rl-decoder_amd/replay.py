@@ -12,18 +12,10 @@ import numpy as np
 import torch
 
 from . import _lib, wire
-from ._lib import check
+from ._lib import _ptr, _stream, check
 from .envset import TransitionBlock
 
 MAX_BATCH = 4096
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def block_capacity(d, nbytes):
