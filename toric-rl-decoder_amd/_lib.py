@@ -8,6 +8,7 @@ import glob
 import os
 import subprocess
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -127,3 +128,46 @@ def check(rc):
         if rc in (TQ_E_INVALID, TQ_E_ACTION, TQ_E_INDEX):
             raise ValueError(f"libtoricenv: {msg}")
         raise ToricEnvError(f"libtoricenv error {rc}: {msg}")
+
+
+def require_gpu(device):
+    """The ``device`` argument of the env surface (None = the current one) -> an indexed cuda device."""
+    if not torch.cuda.is_available():
+        raise ToricEnvError("no HIP device visible to PyTorch-ROCm: the toric env has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError(f"device must be a cuda (ROCm) device, got {dev}")
+    return torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
+
+
+def to_device(x, dtype, device):
+    """numpy array / sequence / tensor (or None) -> contiguous ``dtype`` tensor on ``device`` (or None).  A read-only
+    numpy array (np.broadcast_to, a memory-mapped file) is copied first: torch would alias it as writable."""
+    if x is None:
+        return None
+    if not torch.is_tensor(x):
+        x = torch.as_tensor(np.array(x, copy=True) if isinstance(x, np.ndarray) and not x.flags.writeable else np.ascontiguousarray(x))
+    return x.to(device=device, dtype=dtype).contiguous()
+
+
+class Handle:
+    """An object that owns one library handle ``_h`` on ``device`` (bound library ``_L``): how its calls are issued
+    and how it is destroyed.  ``_h`` is None (or a null pointer) unless a create call succeeded and close() has not run,
+    so close() is safe on a half-constructed object and when called twice."""
+
+    _h = None                       # subclasses also name the symbol that frees it: _destroy
+
+    def _call(self, fn, *args):
+        with torch.cuda.device(self.device):
+            check(fn(self._h, *args, _stream()))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

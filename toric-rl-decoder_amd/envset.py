@@ -20,21 +20,14 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _lib, wire
-from ._lib import TQ_BF16, TQ_F16, TQ_F32, TQ_U8, _ptr, _stream, check
+from . import _lib, stackbuf
+from ._lib import TQ_BF16, TQ_F16, TQ_F32, TQ_U8, Handle, _ptr, _stream, check, require_gpu, to_device
+from .stackbuf import alloc_chunked, alloc_stack, configured_xcd_bias, set_xcd_bias  # noqa: F401
+from .transition import TransitionBlock, generateTransitionParallel, to_structured, transition_dtype, transition_outputs  # noqa: F401
 
 _DTYPES = {torch.float32: TQ_F32, torch.float16: TQ_F16, torch.bfloat16: TQ_BF16, torch.uint8: TQ_U8}
 _STRATEGY = {None: 0, "fixed": 0, "linear": 1, "random": 2}
 SUPPORTED_SIZES = (3, 5, 7, 9, 11, 13, 15, 17, 19, 21)
-
-
-def _require_gpu(device):
-    if not torch.cuda.is_available():
-        raise _lib.ToricEnvError("no HIP device visible to PyTorch-ROCm: the toric env has no CPU fallback")
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError(f"device must be a cuda (ROCm) device, got {dev}")
-    return torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
 
 
 class _ActionSpace:
@@ -114,124 +107,7 @@ def make(env_id, config=None, device=None, seed=0):
     return ToricEnv(config, device=device, seed=seed)
 
 
-class _ChunkedBuffer:
-    """Device memory from tq_stack_alloc, exposed through __cuda_array_interface__ and freed with the last tensor
-    that views it."""
-
-    def __init__(self, nbytes, device):
-        self.ptr = C.c_void_p(None)
-        self.nbytes = int(nbytes)
-        self._L = _lib.load()
-        check(self._L.tq_stack_alloc(device.index, self.nbytes, C.byref(self.ptr)))
-        self.__cuda_array_interface__ = {"shape": (self.nbytes,), "typestr": "|u1", "data": (self.ptr.value, False), "version": 2}
-
-    def __del__(self):
-        try:
-            if self.ptr.value:
-                self._L.tq_stack_free(self.ptr)
-                self.ptr = C.c_void_p(None)
-        except Exception:
-            pass
-
-
-def alloc_chunked(shape, dtype=torch.float32, device=None):
-    """A device tensor of ``shape`` / ``dtype`` in tq_stack_alloc memory: 2 MiB physical chunks behind one virtual
-    range, zero-filled, every page verified to be reached through its own address (include/toricenv.h).  The kind of
-    allocation the stack write ran fastest on in most processes of round 3 (6.5-6.8 TB/s against 5.1-5.5 into
-    torch.empty buffers; on some boxes no kind is faster than another).  The memory is released when the returned
-    tensor (and every view of it) is gone."""
-    dev = _require_gpu(device)
-    shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list, torch.Size)) else (shape,)))
-    nbytes = int(np.prod(shape, dtype=np.int64)) * torch.empty((), dtype=dtype).element_size()
-    holder = _ChunkedBuffer(max(nbytes, 16), dev)
-    with torch.cuda.device(dev):
-        flat = torch.as_tensor(holder, device=dev)            # zero-copy view; keeps `holder` alive
-    return flat[:nbytes].view(dtype).view(shape)
-
-
-def alloc_stack(capacity, size, dtype=torch.float32, device=None):
-    """A stack buffer (capacity, 2, d, d) of ``dtype`` from alloc_chunked (tq_stack_alloc)."""
-    return alloc_chunked((int(capacity), 2, int(size), int(size)), dtype, device)
-
-
-class TransitionBlock:
-    """Packed transition block on the device (layout: include/toricenv.h)."""
-
-    def __init__(self, d, capacity, device):
-        self.d, self.capacity = int(d), int(capacity)
-        nbytes = _lib.load().tq_transition_block_bytes(self.d, self.capacity)
-        if nbytes < 0:
-            raise ValueError("bad transition block shape")
-        self.buf = torch.zeros(max(int(nbytes), 8), dtype=torch.uint8, device=device)
-
-    @property
-    def nbytes(self):
-        return int(self.buf.numel())
-
-    def unpack(self, first=0, count=None, buf=None):
-        """-> dict of device tensors (perspective u8, next_perspective u8, action i32[n,4],
-        reward f32, terminal u8, priority f32) for slots [first, first+count).  Slots without a
-        transition have action op 0 (include/toricenv.h)."""
-        buf = self.buf if buf is None else buf
-        count = self.capacity - first if count is None else int(count)
-        d, dev = self.d, buf.device
-        out = dict(perspective=torch.empty((count, 2, d, d), dtype=torch.uint8, device=dev),
-                   next_perspective=torch.empty((count, 2, d, d), dtype=torch.uint8, device=dev),
-                   action=torch.empty((count, 4), dtype=torch.int32, device=dev),
-                   reward=torch.empty(count, dtype=torch.float32, device=dev),
-                   terminal=torch.empty(count, dtype=torch.uint8, device=dev),
-                   priority=torch.empty(count, dtype=torch.float32, device=dev))
-        with torch.cuda.device(dev):
-            check(_lib.load().tq_transition_unpack(d, _ptr(buf), self.capacity, int(first), count,
-                                                   _ptr(out["perspective"]), _ptr(out["next_perspective"]),
-                                                   _ptr(out["action"]), _ptr(out["reward"]),
-                                                   _ptr(out["terminal"]), _ptr(out["priority"]), _stream()))
-        return out
-
-    def computePriorities(self, no_envs, steps, q_values=None, discount=0.95):
-        """computePrioritiesParallel (util_actor.py:268-287) into the block's priority section for
-        the ``steps`` steps of ``no_envs`` lattices it holds (slot t*no_envs + e).  ``q_values``:
-        device f32 (steps+1, no_envs, 3) -- the q_values of every step plus the step after -- or
-        None for all-zero Q (pure exploration).  No synchronisation."""
-        if q_values is not None:
-            if (q_values.dtype != torch.float32 or not q_values.is_contiguous()
-                    or q_values.numel() != (int(steps) + 1) * int(no_envs) * 3 or q_values.device != self.buf.device):
-                raise ValueError("q_values must be a contiguous float32 device tensor of shape (steps+1, no_envs, 3)")
-        with torch.cuda.device(self.buf.device):
-            check(_lib.load().tq_block_priorities(self.d, _ptr(self.buf), self.capacity, int(no_envs), int(steps),
-                                                  _ptr(q_values), float(discount), _stream()))
-
-
-transition_dtype = wire.transition_type     # the reference's replay record (Actor_mp.py:52-56, util.py:10)
-
-
-def to_structured(unpacked, size):
-    """dict from TransitionBlock.unpack / generateTransition -> numpy array of transition_dtype."""
-    n = unpacked["perspective"].shape[0]
-    rec = np.empty(n, dtype=transition_dtype(size))
-    get = lambda k: unpacked[k].cpu().numpy() if torch.is_tensor(unpacked[k]) else np.asarray(unpacked[k])
-    a = get("action")
-    rec['perspective'] = get("perspective")
-    rec['next_perspective'] = get("next_perspective")
-    rec['action']['position'] = a[:, :3]
-    rec['action']['op'] = a[:, 3]
-    rec['reward'] = get("reward")
-    rec['terminal'] = get("terminal").astype(bool)
-    return rec
-
-
-def configured_xcd_bias():
-    """The process-wide workgroup-share setting (toricenv.h: tq_set_xcd_bias; the library's default or TORICENV_XCD_BIAS).
-    pickStackBuffer's check decides per EnvSet (tq_env_set_xcd_bias) and leaves this alone."""
-    return int(_lib.load().tq_get_xcd_bias())
-
-
-def set_xcd_bias(bias):
-    """tq_set_xcd_bias for this process."""
-    check(_lib.load().tq_set_xcd_bias(int(bias)))
-
-
-class EnvSet:
+class EnvSet(Handle):
     """Batch of N toric-code lattices resident on one MI355X (reference: src/EnvSet.py:4-51).
 
     ``env`` is a :class:`ToricEnv` (or anything with ``system_size`` and optionally
@@ -242,11 +118,14 @@ class EnvSet:
 
     def __init__(self, env, no_envs, device=None, seed=None, first_env_id=0, numpy_io=True,
                  max_steps_per_episode=75):
+        self._parked = []               # candidates pickStackBuffer(park=True) rejected, until releaseParked() / close()
+        self._stack_cache = None        # generatePerspectiveReused's buffer: dict(dtype, capacity, buf, pos, probe)
+        self._positions = None          # positions of the last stack written: selectAction's default
         self._h = C.c_void_p(None)
         self.size = int(env.system_size)
         self.no_envs = int(no_envs)
         self.numpy_io = bool(numpy_io)
-        self.device = _require_gpu(device if device is not None else getattr(env, "device", None))
+        self.device = require_gpu(device if device is not None else getattr(env, "device", None))
         self.seed = int(getattr(env, "seed", 0) if seed is None else seed)
         self.first_env_id = int(first_env_id)
         self.p_error = float(getattr(env, "p_error", 0.1))
@@ -270,37 +149,25 @@ class EnvSet:
         self._qv = torch.zeros((n, 3), dtype=torch.float32, device=dev)
         self._counts = torch.zeros(n, dtype=torch.int32, device=dev)
         self._offsets = torch.zeros(n + 1, dtype=torch.int64, device=dev)
-        self._positions = None
         # attributes of the reference class (EnvSet.py:9-11)
         self.states = np.zeros((n, 2, d, d), dtype=np.int64)
         self.rewards = np.zeros(n)
         self.terminals = np.zeros(n, dtype=bool)
 
     # ------------------------------------------------------------------ plumbing
+    _destroy = "tq_destroy"
+
     def close(self):
         self._parked = []
-        self.__dict__.pop("_stack_cache", None)
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.tq_destroy(self._h)
-            self._h = C.c_void_p(None)
+        self._stack_cache = None
+        super().close()
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _call(self, fn, *args):
-        with torch.cuda.device(self.device):
-            check(fn(self._h, *args, _stream()))
-
-    def _dev(self, x, dtype):
-        if x is None:
-            return None
-        if torch.is_tensor(x):
-            return x.to(device=self.device, dtype=dtype).contiguous()
-        x = np.array(x, copy=True) if isinstance(x, np.ndarray) and not x.flags.writeable else np.ascontiguousarray(x)
-        return torch.as_tensor(x, device=self.device).to(dtype).contiguous()
+    def _out(self, x, dtype=None):
+        """The numpy_io return convention: the device tensor itself, or its host copy (as ``dtype``, the reference's)."""
+        if not self.numpy_io:
+            return x
+        x = x.cpu().numpy()
+        return x if dtype is None else x.astype(dtype)
 
     def check(self):
         """Raise if a kernel latched an error (bad action / capacity).  Synchronises."""
@@ -315,17 +182,17 @@ class EnvSet:
     # ------------------------------------------------------------------ reference surface
     def resetAll(self, p_errors=None):
         """EnvSet.py:29-36 -> states (N,2,d,d) (int64 numpy / uint8 tensor)."""
-        p = self._dev(p_errors, torch.float64)
+        p = to_device(p_errors, torch.float64, self.device)
         if p is not None and p.numel() != self.no_envs:
             raise ValueError("p_errors must have one entry per env")
         self._call(self._L.tq_reset_all, _ptr(p))
-        return self._return_states()
+        return self.getStates()
 
     def resetTerminalEnvs(self, idx, p_errors=None):
         """EnvSet.py:19-27 -> states of the reset lattices (len(idx),2,d,d) (float64 numpy)."""
-        idx_t = self._dev(idx, torch.int32)
+        idx_t = to_device(idx, torch.int32, self.device)
         k = int(idx_t.numel())
-        p = self._dev(p_errors, torch.float64)
+        p = to_device(p_errors, torch.float64, self.device)
         if p is not None and p.numel() != k:
             raise ValueError("p_errors must have one entry per idx")
         if self.numpy_io and k:
@@ -337,40 +204,36 @@ class EnvSet:
             # the device checks idx as well (range, duplicates) and latches TQ_E_INDEX for check()
             self._call(self._L.tq_reset_idx, _ptr(idx_t), k, _ptr(p))
             self._call(self._L.tq_get_state_idx, _ptr(idx_t), k, _ptr(out))
-        return out.cpu().numpy().astype(np.float64) if self.numpy_io else out
+        return self._out(out, np.float64)
 
     def step(self, actions):
         """EnvSet.py:38-47 -> (states, rewards, terminals, info)."""
-        a = self._dev(actions, torch.int32)
+        a = to_device(actions, torch.int32, self.device)
         if a.numel() != 4 * self.no_envs:
             raise ValueError("actions must be (no_envs, 4)")
         self._actions.copy_(a.reshape(self.no_envs, 4))
         self._call(self._L.tq_step, _ptr(self._actions), _ptr(self._rewards), _ptr(self._terminals))
-        states = self._return_states()
+        states = self.getStates()
         if self.numpy_io:
             self.check()
-            self.rewards = self._rewards.cpu().numpy().astype(np.float64)
-            self.terminals = self._terminals.cpu().numpy().astype(bool)
+            self.rewards, self.terminals = self._out(self._rewards, np.float64), self._out(self._terminals, bool)
             return states, self.rewards, self.terminals, {}
         return states, self._rewards, self._terminals, {}
 
-    def _return_states(self):
+    def getStates(self):
         self._call(self._L.tq_get_state, _ptr(self._state_u8))
         if self.numpy_io:
-            self.states = self._state_u8.cpu().numpy().astype(np.int64)
+            self.states = self._out(self._state_u8, np.int64)
             return self.states
         return self._state_u8
-
-    def getStates(self):
-        return self._return_states()
 
     def getQubits(self):
         q = torch.empty((self.no_envs, 2, self.size, self.size), dtype=torch.uint8, device=self.device)
         self._call(self._L.tq_get_qubits, _ptr(q))
-        return q.cpu().numpy().astype(np.int64) if self.numpy_io else q
+        return self._out(q, np.int64)
 
     def setQubits(self, qubits):
-        q = self._dev(qubits, torch.uint8)
+        q = to_device(qubits, torch.uint8, self.device)
         if q.numel() != self.no_envs * 2 * self.size * self.size:
             raise ValueError("qubits must be (no_envs, 2, d, d)")
         self._call(self._L.tq_set_qubits, _ptr(q))
@@ -379,17 +242,17 @@ class EnvSet:
         ep = torch.empty(self.no_envs, dtype=torch.int32, device=self.device)
         st = torch.empty(self.no_envs, dtype=torch.int32, device=self.device)
         self._call(self._L.tq_get_counters, _ptr(ep), _ptr(st))
-        return (ep.cpu().numpy(), st.cpu().numpy()) if self.numpy_io else (ep, st)
+        return self._out(ep), self._out(st)
 
     def evalGroundState(self):
         out = torch.empty(self.no_envs, dtype=torch.uint8, device=self.device)
         self._call(self._L.tq_eval_ground_state, _ptr(out))
-        return out.cpu().numpy().astype(bool) if self.numpy_io else out
+        return self._out(out, bool)
 
     def isTerminal(self):
         out = torch.empty(self.no_envs, dtype=torch.uint8, device=self.device)
         self._call(self._L.tq_is_terminal, _ptr(out))
-        return out.cpu().numpy().astype(bool) if self.numpy_io else out
+        return self._out(out, bool)
 
     # ------------------------------------------------------------------ perspectives
     def perspectiveCounts(self, offsets=None):
@@ -423,138 +286,63 @@ class EnvSet:
         self._positions = positions
 
     def pickStackBuffer(self, candidates=4, dtype=torch.float32, capacity=None, positions=None, launches=10,
-                        kinds=("torch", "chunked"), park=False, first=0, count=None, timer=None, passes=2, among=None,
-                        check_shares=True, extend_if_uniform=True):
+                        kinds=("torch", "chunked"), park=False, timer=None, passes=2, among=None):
         """Set-up helper: allocate ``candidates`` stack buffers (``capacity`` perspectives each, default the worst
         case no_envs * 2*d*d), time the stack write on each of them and keep the fastest.  On MI355X the rate of a
         write stream into a buffer depends on the buffer AND on the stream's shape (5.2-6.9 TB/s for this kernel,
         from allocation to allocation; a buffer that is fast for the f32 stack can be slow for the bf16 stack of the
         same lattices: profiles/r04_stream_tune_d7_all.txt), and a caller writes the same buffer every step, so the
-        choice is worth a few dozen launches at set-up -- per dtype.
-        ALL candidates are allocated first (and stay allocated while the timing runs), then every candidate is timed
-        ``passes`` times in turn, ``launches`` writes in all, and the MEDIAN decides.  ``timer(stack, k)`` -> list of
-        k write times in ms: what is timed -- default: scan + write of the current lattices, back to back;
-        ExploreLoop.time_writes times the write inside the caller's loop, the env kernels beside it.
-        ``kinds``: where the candidates come from -- kinds[0] for candidate 0, the rest cyclically for the others:
-        "torch" = torch.empty (candidate 0 by default: what a caller has without this helper), "chunked" = alloc_stack
-        (2 MiB physical chunks).  ``among``: time these tensors instead of allocating (a re-probe of parked candidates).
+        choice is worth a few dozen launches at set-up -- per dtype.  The steps (stackbuf.py has each of them):
+        1. ALL candidates are allocated first, as many as half of the free memory holds, and stay allocated while the
+           timing runs.  ``kinds``: where they come from -- kinds[0] for candidate 0, the rest cyclically for the
+           others: "torch" = torch.empty (candidate 0 by default: what a caller has without this helper), "chunked" =
+           alloc_stack (2 MiB physical chunks).  ``among``: time these tensors instead of allocating (a re-probe of
+           parked candidates).
+        2. Every candidate is timed ``passes`` times in turn, ``launches`` writes in all.  ``timer(stack, k)`` -> list
+           of k write times in ms: what is timed -- default: scan + write of the current lattices, back to back;
+           ExploreLoop.time_writes times the write inside the caller's loop, the env kernels beside it.
+        3. When no candidate writes 7 % faster than candidate 0, as many candidates again are allocated and timed (the
+           first ones stay allocated) -- once.
+        4. The MEDIAN decides.  ``park``: keep the rejected candidates allocated until releaseParked() / close()
+           instead of freeing them here -- the driver wipes freed device memory in the background, tens of GB of it
+           take HBM bandwidth away from whatever runs in the next tens of milliseconds (a benchmark's timed region, say).
+        5. The kept buffer is timed with equal shares per workgroup against the library's unequal ones (toricenv.h:
+           tq_set_xcd_bias) and the faster setting is kept for this EnvSet (report["xcd_bias"]).
         -> (stack tensor (capacity,2,d,d), report dict: median / min ms and kind of every candidate, which was kept).
-        ``park``: keep the rejected candidates allocated until releaseParked() / close() instead of freeing them here
-        -- the driver wipes freed device memory in the background, tens of GB of it take HBM bandwidth away from
-        whatever runs in the next tens of milliseconds (a benchmark's timed region, say).
-        ``first`` / ``count``: the default timer writes that lattice range only (a consumer that walks the batch in ranges
-        with a small buffer: ``capacity`` is then the small buffer's).  ``check_shares``: also time the kept buffer with
-        equal shares per workgroup against the library's unequal ones (toricenv.h: tq_set_xcd_bias) and keep the faster
-        setting (report["xcd_bias"]).  ``extend_if_uniform``: when no candidate writes 7 % faster than candidate 0, allocate
-        and time as many candidates again (the first ones stay allocated; bounded by half of the free memory) -- once.
         Synchronises; never call it in the step loop."""
         d, nq = self.size, 2 * self.size * self.size
         cap = self.no_envs * nq if capacity is None else int(capacity)
         if positions is None:
             positions = torch.empty((cap, 3), dtype=torch.int32, device=self.device)
-        keep, used = [], []
+        shape, passes = (cap, 2, d, d), max(1, int(passes))
+        per_pass = max(1, int(launches) // passes)
         if among is not None:
-            keep = list(among)
-            used = ["re-probed"] * len(keep)
+            keep, used, room = list(among), [stackbuf.REPROBED] * len(among), 0
         else:
-            # all candidates exist at once: never more of them than half of the free device memory holds
-            nbytes = cap * nq * torch.empty((), dtype=dtype).element_size()
+            keep, used = [], []
             with torch.cuda.device(self.device):
                 free = torch.cuda.mem_get_info()[0]
-            wanted = max(1, int(candidates))
-            room = int(0.5 * free // max(nbytes, 1))              # candidates that may exist at once
-            fit = max(1, min(wanted, room))
-
-            def allocate(count):
-                """``count`` more candidates (fewer when the device runs out); -> how many there are now."""
-                for _ in range(count):
-                    k = len(keep)
-                    kind = kinds[0] if k == 0 or len(kinds) == 1 else kinds[1 + (k - 1) % (len(kinds) - 1)]
-                    c = None
-                    try:
-                        if kind == "chunked":
-                            try:
-                                c = alloc_stack(cap, d, dtype, self.device)
-                            except _lib.ToricEnvError:            # no virtual-memory API on this driver (or no memory): plain allocation
-                                kind = "torch"
-                        if c is None:
-                            c = torch.empty((cap, 2, d, d), dtype=dtype, device=self.device)
-                    except torch.OutOfMemoryError:
-                        if not keep:
-                            raise
-                        break                                     # the candidates that exist will do
-                    used.append("torch.empty" if kind == "torch" else "alloc_stack (2 MiB chunks)")
-                    keep.append(c)
-                    c = None
-                return len(keep)
-            allocate(fit)
+            room, fit = stackbuf.candidates_that_fit(free, cap * nq * torch.empty((), dtype=dtype).element_size(), candidates)
+            stackbuf.allocate_candidates(keep, used, fit, kinds, shape, dtype, self.device)
         if timer is None:
-            off = self.perspectiveCounts()[1].clone()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-
-            def timer(stack, k):
-                out = []
-                for r in range(k + 1):
-                    e0.record()
-                    self.writePerspectives(stack, positions, off, first=first, count=count)
-                    e1.record()
-                    e1.synchronize()
-                    out.append(e0.elapsed_time(e1))
-                return out[1:]
+            timer = stackbuf.default_timer(self, positions)
         torch.cuda.synchronize(self.device)
-        per_pass = max(1, int(launches) // max(1, int(passes)))
-        samples = [[] for _ in keep]
-        for _ in range(max(1, int(passes))):
-            for i, c in enumerate(keep):
-                samples[i] += list(timer(c, per_pass))
-        # No candidate stands out (every one within 7 % of candidate 0)?  On some boxes the first tens of GB a process
-        # allocates ALL write at the slow rate and faster buffers only turn up behind them (profiles/README.md, round 4:
-        # 24 x 2.5 GB at 0.358-0.368 ms, then, for the next leg, candidates 12 and 16-20 of 24 x 5 GB at 0.57 against 0.71 ms).
-        # So the search goes on once, with as many candidates again, WHILE the first ones stay allocated.
-        extended = 0
-        if among is None and extend_if_uniform and len(keep) >= 3 and len(keep) < room:
-            ms0 = [float(np.median(x)) for x in samples]
-            if min(ms0) > 0.93 * ms0[0] and ms0[0] >= 0.1:         # (a write of under 0.1 ms is not about bandwidth)
-                before = len(keep)
-                extended = allocate(min(before, room - before)) - before
-                samples += [[] for _ in range(extended)]
-                torch.cuda.synchronize(self.device)
-                for _ in range(max(1, int(passes))):
-                    for i in range(before, len(keep)):
-                        samples[i] += list(timer(keep[i], per_pass))
+        samples = stackbuf.time_candidates(timer, keep, passes, per_pass)
+        first, more = len(keep), stackbuf.candidates_to_add(stackbuf.medians(samples), room, among is not None)
+        if more:
+            stackbuf.allocate_candidates(keep, used, more, kinds, shape, dtype, self.device)
+            torch.cuda.synchronize(self.device)
+            samples += stackbuf.time_candidates(timer, keep[first:], passes, per_pass)
         self.check()
-        ms = [float(np.median(x)) for x in samples]
-        chosen = int(np.argmin(ms))
-        best = keep[chosen]
-        rejected = [x for x in keep if x is not best]
+        best = keep[stackbuf.verdict(samples)[2]]
         if park:
-            self._parked = [x for x in getattr(self, "_parked", []) if all(x is not y for y in keep)] + rejected
-        report = {"candidates": len(ms), "candidates_asked": int(candidates) if among is None else len(ms), "candidates_added_because_uniform": extended, "write_ms": ms, "write_ms_min": [float(min(x)) for x in samples], "chosen": chosen,
-                  "probe_ms_chosen": ms[chosen], "writes_per_candidate": len(samples[0]), "kinds": used,
-                  "addresses": [hex(x.data_ptr()) for x in keep]}
-        # The shares of the write's workgroups (tq_set_xcd_bias: the even XCDs' workgroups take more of the stack) against
-        # equal shares, on the buffer that was kept: the setting rests on a measured asymmetry of MI355X, so it is checked
-        # where it is used.  The outcome is set on this EnvSet's handle only; d <= 5 and u8 stacks never use unequal shares.
-        if check_shares and d >= 7 and dtype != torch.uint8:
-            L = self._L
-            b0 = int(L.tq_get_xcd_bias())                       # the process-wide setting; the decision is this HANDLE's own
-            if b0 > 0:
-                check(L.tq_env_set_xcd_bias(self._h, 0))
-                eq = float(np.median(list(timer(best, per_pass)) + list(timer(best, per_pass))))
-                check(L.tq_env_set_xcd_bias(self._h, b0))
-                un = float(np.median(list(timer(best, per_pass)) + list(timer(best, per_pass))))
-                keep_bias = un <= eq
-                check(L.tq_env_set_xcd_bias(self._h, -1 if keep_bias else 0))
-                report["xcd_bias"] = {"bias": b0 if keep_bias else 0, "write_ms_biased": un, "write_ms_equal_shares": eq}
-                report["probe_ms_chosen"] = min(un, eq)
-            else:
-                report["xcd_bias"] = {"bias": 0}
-        del keep, rejected
+            self._parked = [x for x in self._parked if all(x is not y for y in keep)] + [x for x in keep if x is not best]
+        shares = stackbuf.check_shares(self, timer, best, per_pass, dtype)
+        report = stackbuf.probe_report(samples, int(candidates) if among is None else len(keep), len(keep) - first, used,
+                                       [hex(x.data_ptr()) for x in keep], shares)
+        del keep
         if not park:
             torch.cuda.empty_cache()
-        if len(ms) > 2 and min(ms) > 0.9 * ms[0]:
-            report["uniform"] = ("no candidate writes more than 10 % faster than candidate 0: on some boxes every buffer -- and "
-                                 "every write stream, hipMemset included -- runs at one rate (profiles/r03_stack_write_ab.txt)")
         return best, report
 
     def releaseParked(self):
@@ -579,25 +367,17 @@ class EnvSet:
         counts, offsets = self.perspectiveCounts()
         P = int(offsets[-1].item())
         worst = self.no_envs * nq
-        cache = self.__dict__.get("_stack_cache")
+        cache = self._stack_cache
         if cache is None or cache["dtype"] != dtype or cache["capacity"] < P or (capacity is not None and cache["capacity"] < min(int(capacity), worst)):
             want = min(worst, max(int(capacity) if capacity is not None else int(P * self.REUSED_HEADROOM) + 1024, P, 1024))
-            self.__dict__.pop("_stack_cache", None)
-            cache = None
+            cache = self._stack_cache = None
             torch.cuda.empty_cache()
-            try:
-                pos = alloc_chunked((want, 3), torch.int32, self.device)
-            except _lib.ToricEnvError:                            # no virtual-memory API on this driver
-                pos = torch.empty((want, 3), dtype=torch.int32, device=self.device)
+            pos = stackbuf.alloc_kind("chunked", (want, 3), torch.int32, self.device)[0]
             k = int(self.REUSED_PROBE_CANDIDATES)
             if k > 1 and P > 0:
                 buf, report = self.pickStackBuffer(k, dtype=dtype, capacity=want, positions=pos, launches=6, passes=2)
             else:
-                try:
-                    buf = alloc_stack(want, d, dtype, self.device)
-                except _lib.ToricEnvError:
-                    buf = torch.empty((want, 2, d, d), dtype=dtype, device=self.device)
-                report = None
+                buf, report = stackbuf.alloc_kind("chunked", (want, 2, d, d), dtype, self.device)[0], None
             cache = self._stack_cache = {"dtype": dtype, "capacity": want, "buf": buf, "pos": pos, "probe": report}
         buf, pos = cache["buf"], cache["pos"]
         if P:
@@ -607,8 +387,7 @@ class EnvSet:
 
     def reusedStackBacking(self):
         """The whole buffer behind the last generatePerspectiveReused result (rows past P are slack)."""
-        c = self.__dict__.get("_stack_cache")
-        return None if c is None else c["buf"]
+        return None if self._stack_cache is None else self._stack_cache["buf"]
 
     def generatePerspective(self, states=None, dtype=torch.float32):
         """generatePerspectiveBatch + concatenate (numba/util_actor.py:33-39,56-67) for the current
@@ -616,21 +395,16 @@ class EnvSet:
         -> (perspectives (P,2,d,d), positions (P,3), counts (N,)).
         Reads P back from the device (one 8-byte copy), like the reference's data-dependent shape."""
         if states is not None:
-            out, pos, counts = generatePerspectiveBatch(self.size // 2, self.size, states, dtype=dtype, device=self.device)[:3]
-            if self.numpy_io:
-                return out.cpu().numpy(), pos.cpu().numpy().astype(np.int64), counts.cpu().numpy().astype(np.int64)
-            return out, pos, counts
-        counts, offsets = self.perspectiveCounts()
-        P = int(offsets[-1].item())
-        d = self.size
-        out = torch.empty((P, 2, d, d), dtype=dtype, device=self.device)
-        pos = torch.empty((P, 3), dtype=torch.int32, device=self.device)
-        if P:
-            self.writePerspectives(out, pos, offsets)
-        self._positions = pos
-        if self.numpy_io:
-            return out.cpu().numpy(), pos.cpu().numpy().astype(np.int64), counts.cpu().numpy().astype(np.int64)
-        return out, pos, counts
+            out, pos, counts = generatePerspectiveBatch(self.size // 2, self.size, states, dtype=dtype, device=self.device)
+        else:
+            counts, offsets = self.perspectiveCounts()
+            P = int(offsets[-1].item())
+            out = torch.empty((P, 2, self.size, self.size), dtype=dtype, device=self.device)
+            pos = torch.empty((P, 3), dtype=torch.int32, device=self.device)
+            if P:
+                self.writePerspectives(out, pos, offsets)
+            self._positions = pos
+        return self._out(out), self._out(pos, np.int64), self._out(counts, np.int64)
 
     # ------------------------------------------------------------------ policy glue
     def selectAction(self, q_table, eps, positions=None, offsets=None):
@@ -639,32 +413,26 @@ class EnvSet:
         pos = self._positions if positions is None else positions
         if pos is None:
             raise ValueError("call generatePerspective / writePerspectives (with positions) first")
-        pos = self._dev(pos, torch.int32)
-        off = self._offsets if offsets is None else self._dev(offsets, torch.int64)
-        q = self._dev(q_table, torch.float32)
-        e = None
-        if q is not None:
-            e = self._dev(np.broadcast_to(np.asarray(eps, np.float64), (self.no_envs,)) if not torch.is_tensor(eps) else eps,
-                          torch.float64)
+        pos = to_device(pos, torch.int32, self.device)
+        off = self._offsets if offsets is None else to_device(offsets, torch.int64, self.device)
+        q = to_device(q_table, torch.float32, self.device)
+        if q is not None and not torch.is_tensor(eps):
+            eps = np.broadcast_to(np.asarray(eps, np.float64), (self.no_envs,))
+        e = None if q is None else to_device(eps, torch.float64, self.device)
         self._call(self._L.tq_select_action, _ptr(q), _ptr(off), _ptr(pos), _ptr(e), _ptr(self._actions), _ptr(self._qv))
-        if self.numpy_io:
-            return self._actions.cpu().numpy().astype(np.int64), self._qv.cpu().numpy()
-        return self._actions, self._qv
+        return self._out(self._actions, np.int64), self._out(self._qv)
 
     def generateTransition(self, actions):
         """generateTransitionParallel for the last step() (util_actor.py:223-264)
         -> dict(perspective u8, next_perspective u8, action i32[N,4]) of device tensors
         (numpy arrays with numpy_io)."""
-        a = self._dev(actions, torch.int32)
-        n, d, dev = self.no_envs, self.size, self.device
-        out = dict(perspective=torch.empty((n, 2, d, d), dtype=torch.uint8, device=dev),
-                   next_perspective=torch.empty((n, 2, d, d), dtype=torch.uint8, device=dev),
-                   action=torch.empty((n, 4), dtype=torch.int32, device=dev))
+        a = to_device(actions, torch.int32, self.device)
+        out = transition_outputs(self.no_envs, self.size, self.device)
         self._call(self._L.tq_transition_write, _ptr(a), _ptr(out["perspective"]), _ptr(out["next_perspective"]),
                    _ptr(out["action"]))
         if self.numpy_io:
             self.check()
-            return {k: v.cpu().numpy() for k, v in out.items()}
+            return {k: self._out(v) for k, v in out.items()}
         return out
 
     def newTransitionBlock(self, steps=1):
@@ -675,7 +443,7 @@ class EnvSet:
         actions None = pure exploration drawn in-kernel.  ``block``/``slot``: lattice e writes
         transition slot ``slot*no_envs + e`` of the TransitionBlock.
         -> (actions_taken i32[N,4], rewards f32[N], terminals u8[N]) device tensors."""
-        a = self._dev(actions, torch.int32)
+        a = to_device(actions, torch.int32, self.device)
         blk_ptr, cap, base = C.c_void_p(0), 0, 0
         if block is not None:
             blk_ptr, cap, base = _ptr(block.buf), block.capacity, int(slot) * self.no_envs
@@ -683,8 +451,7 @@ class EnvSet:
                    _ptr(self._rewards), _ptr(self._terminals), blk_ptr, cap, base)
         if self.numpy_io:
             self.check()
-            return (self._actions.cpu().numpy().astype(np.int64), self._rewards.cpu().numpy().astype(np.float64),
-                    self._terminals.cpu().numpy().astype(bool))
+            return self._out(self._actions, np.int64), self._out(self._rewards, np.float64), self._out(self._terminals, bool)
         return self._actions, self._rewards, self._terminals
 
 
@@ -707,12 +474,11 @@ def generatePerspectiveBatch(grid_shift, toric_size, states, dtype=torch.float32
     -> (perspectives (P,2,d,d) tensor, positions (P,3) i32 tensor, counts (n,) i32 tensor)
     [+ offsets (n+1,) i64 tensor, the exclusive scan the kernels produced, with ``return_offsets``].
     One 8-byte read-back of P (the output shape is data dependent, as upstream)."""
-    dev = _require_gpu(device)
+    dev = require_gpu(device)
     if int(grid_shift) != int(toric_size) // 2:
         raise ValueError("grid_shift must be int(toric_size/2) (Actor_mp.py:59)")
     L = _lib.load()
-    st = states if torch.is_tensor(states) else torch.as_tensor(np.ascontiguousarray(states))
-    st = st.to(device=dev, dtype=torch.uint8).contiguous()
+    st = to_device(states, torch.uint8, dev)
     n, d = int(st.shape[0]), int(toric_size)
     counts = torch.empty(n, dtype=torch.int32, device=dev)
     offsets = torch.empty(n + 1, dtype=torch.int64, device=dev)
@@ -731,28 +497,3 @@ def generatePerspectiveBatch(grid_shift, toric_size, states, dtype=torch.float32
             check(L.tq_states_persp_write(d, n, _ptr(st), _ptr(offsets), _ptr(out), _ptr(pos), P, _DTYPES[dtype],
                                           _stream()))
     return (out, pos, counts, offsets) if return_offsets else (out, pos, counts)
-
-
-def generateTransitionParallel(action, reward, state, next_state, terminal_state, grid_shift, trans_type=None,
-                               device=None):
-    """Drop-in for src/util_actor.py:223-264 on the GPU: same arguments, returns a numpy record
-    array of ``trans_type`` (default: transition_dtype(size), Actor_mp.py:52-56)."""
-    dev = _require_gpu(device)
-    L = _lib.load()
-    st = torch.as_tensor(np.ascontiguousarray(state)).to(device=dev, dtype=torch.uint8).contiguous()
-    nst = torch.as_tensor(np.ascontiguousarray(next_state)).to(device=dev, dtype=torch.uint8).contiguous()
-    act = torch.as_tensor(np.ascontiguousarray(action)).to(device=dev, dtype=torch.int32).contiguous()
-    n, d = int(nst.shape[0]), int(nst.shape[-1])
-    if int(grid_shift) != d // 2:
-        raise ValueError("grid_shift must be int(toric_size/2) (Actor_mp.py:59)")
-    out = dict(perspective=torch.empty((n, 2, d, d), dtype=torch.uint8, device=dev),
-               next_perspective=torch.empty((n, 2, d, d), dtype=torch.uint8, device=dev),
-               action=torch.empty((n, 4), dtype=torch.int32, device=dev))
-    with torch.cuda.device(dev):
-        check(L.tq_states_transition(d, n, _ptr(st), _ptr(nst), _ptr(act), _ptr(out["perspective"]),
-                                     _ptr(out["next_perspective"]), _ptr(out["action"]), _stream()))
-        check(L.tq_states_check(_stream()))                       # bad action -> ValueError
-    out["reward"] = np.asarray(reward, np.float64)
-    out["terminal"] = np.asarray(terminal_state, bool)
-    rec = to_structured(out, d)
-    return rec if trans_type is None else rec.astype(trans_type)

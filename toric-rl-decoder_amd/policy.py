@@ -15,8 +15,8 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import check
-from .envset import EnvSet, ToricEnv, _ptr, _stream, generatePerspectiveBatch
+from ._lib import _ptr, _stream, check, to_device
+from .envset import EnvSet, ToricEnv, generatePerspectiveBatch
 
 
 class NN_11(nn.Module):
@@ -85,9 +85,7 @@ def selectActionEnvSet(envs, model, epsilon, dtype=torch.float32, chunk=1 << 16)
         act, qv = envs.selectAction(q, epsilon, positions=pos)
     finally:
         envs.numpy_io = io
-    if io:
-        return act.cpu().numpy().astype(np.int64), qv.cpu().numpy()
-    return act, qv
+    return envs._out(act, np.int64), envs._out(qv)
 
 
 # The reference's selectActionBatch draws from numpy's global RNG, which nothing ever seeds
@@ -101,6 +99,27 @@ def seed_select(seed, calls=0):
     _select_rng["calls"] = int(calls)
 
 
+def _cuda_only(device):
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("device must be a cuda (ROCm) device: the toric env has no CPU path")
+    return dev
+
+
+def _select_action_launch(n, q, offsets, pos, eps, launch=True):
+    """One tq_states_select_action call for ``n`` states: takes the next call number of the Philox stream (taken
+    even when ``launch`` is false) -> (actions i32 (n,4), q_values f32 (n,3)) device tensors."""
+    actions = torch.empty((n, 4), dtype=torch.int32, device=q.device)
+    qv = torch.empty((n, 3), dtype=torch.float32, device=q.device)
+    call = _select_rng["calls"]
+    _select_rng["calls"] = call + 1
+    if launch:
+        with torch.cuda.device(q.device):
+            check(_lib.load().tq_states_select_action(n, _ptr(q), _ptr(offsets), _ptr(pos), _ptr(eps),
+                                                      _select_rng["seed"], call, 0, _ptr(actions), _ptr(qv), _stream()))
+    return actions, qv
+
+
 def selectActionBatch(number_of_actions, epsilon, grid_shift, toric_size, state, model, device, chunk=1 << 16):
     """Drop-in for src/numba/util_actor.py:11-53 -- same argument names, order and return types:
     ``state`` (N,2,d,d) numpy array (or tensor), ``epsilon`` scalar or (N,) array, ``device`` the
@@ -111,22 +130,13 @@ def selectActionBatch(number_of_actions, epsilon, grid_shift, toric_size, state,
     (the reference would raise on it, :93) gets action op 0 and zero q_values."""
     if int(number_of_actions) != 3:
         raise ValueError("number_of_actions must be 3 (env.action_space.high[-1], Actor_mp.py:58)")
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("device must be a cuda (ROCm) device: the toric env has no CPU path")
+    dev = _cuda_only(device)
     model.eval()
     persp, pos, counts, offsets = generatePerspectiveBatch(grid_shift, toric_size, state, device=dev, return_offsets=True)
-    dev = persp.device
     n = int(counts.numel())
     q = _forward_chunked(model, persp, chunk)
-    eps = torch.as_tensor(np.array(np.broadcast_to(np.asarray(epsilon, np.float64), (n,))), device=dev)   # writable copy
-    actions = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    qv = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    call = _select_rng["calls"]
-    _select_rng["calls"] = call + 1
-    with torch.cuda.device(dev):
-        check(_lib.load().tq_states_select_action(n, _ptr(q), _ptr(offsets), _ptr(pos), _ptr(eps),
-                                                  _select_rng["seed"], call, 0, _ptr(actions), _ptr(qv), _stream()))
+    eps = to_device(np.broadcast_to(np.asarray(epsilon, np.float64), (n,)), torch.float64, persp.device)
+    actions, qv = _select_action_launch(n, q, offsets, pos, eps)       # zero states: the shell's ValueError
     return actions.cpu().numpy().astype(np.int64), qv.cpu().numpy().astype(np.float64)
 
 
@@ -137,31 +147,20 @@ def _selectActionBatch_prime(q_values_table, splice_idx, positions, greedy, devi
     first (perspective, op) attaining the maximum of the state's slice in row-major order (:93-95); otherwise a
     uniform perspective and op (:97-98) from the Philox stream of seed_select() (upstream: numpy's unseeded global
     RNG).  A state with an empty slice (the reference raises on it) gets action op 0 and zero q_values."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if dev.type != "cuda":
-        raise ValueError("device must be a cuda (ROCm) device: the toric env has no CPU path")
-    q = torch.as_tensor(np.ascontiguousarray(q_values_table) if not torch.is_tensor(q_values_table) else q_values_table)
-    q = q.to(device=dev, dtype=torch.float32).contiguous()
-    sp = torch.as_tensor(np.asarray(splice_idx, np.int64) if not torch.is_tensor(splice_idx) else splice_idx).to(dev, torch.int64)
+    dev = _cuda_only(torch.device("cuda", torch.cuda.current_device()) if device is None else device)
+    q = to_device(q_values_table, torch.float32, dev)
+    sp = to_device(splice_idx, torch.int64, dev)
     n = int(sp.numel())
     offsets = torch.zeros(n + 2, dtype=torch.int64, device=dev)[:n + 1]       # even length behind it: 16-byte aligned rows
     offsets[1:] = sp
-    pos = torch.as_tensor(np.ascontiguousarray(positions) if not torch.is_tensor(positions) else positions)
-    pos = pos.to(device=dev, dtype=torch.int32).contiguous()
+    pos = to_device(positions, torch.int32, dev)
     if q.shape[0] != pos.shape[0] or (n and int(sp[-1].item()) != q.shape[0]):
         raise ValueError("q_values_table / positions / splice_idx do not describe the same perspectives")
-    g = torch.as_tensor(np.asarray(greedy, bool) if not torch.is_tensor(greedy) else greedy).to(dev)
+    g = to_device(greedy, torch.bool, dev)
     if g.numel() != n:
         raise ValueError("greedy must have one entry per state")
-    eps = (~g.bool()).to(torch.float64).contiguous()          # greedy iff (1 - eps) > U with U in [0,1): eps 0 -> always, 1 -> never
-    actions = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    qv = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    call = _select_rng["calls"]
-    _select_rng["calls"] = call + 1
-    if n:
-        with torch.cuda.device(dev):
-            check(_lib.load().tq_states_select_action(n, _ptr(q), _ptr(offsets), _ptr(pos), _ptr(eps),
-                                                      _select_rng["seed"], call, 0, _ptr(actions), _ptr(qv), _stream()))
+    eps = (~g).to(torch.float64).contiguous()                 # greedy iff (1 - eps) > U with U in [0,1): eps 0 -> always, 1 -> never
+    actions, qv = _select_action_launch(n, q, offsets, pos, eps, launch=n > 0)     # no states: empty arrays, no launch
     return actions.cpu().numpy().astype(np.float64), qv.cpu().numpy().astype(np.float64)
 
 
@@ -212,6 +211,28 @@ def _greedy_episodes(envs, model, epsilon, num_of_steps, chunk):
     return dict(done=done, n_steps=n_steps, q_sum=q_sum, q_cnt=q_cnt)
 
 
+def _close_p_error(envs, r, gs, round_like_reference):
+    """The end of one p_error of evaluate / prediction_smart: the error latch is read, the lattices are freed
+    -> (share of episodes solved, share in the ground state, mean steps, mean Q of the chosen actions) from the episodes'
+    outcome ``r`` (_greedy_episodes) and ``gs`` (evalGroundState, bool tensor)."""
+    steps, mean_q = float(r["n_steps"].double().mean()), float(r["q_sum"] / r["q_cnt"].clamp(min=1))
+    if round_like_reference:
+        steps, mean_q = np.round(steps, 1), np.round(mean_q, 3)
+    envs.check()
+    envs.close()
+    return float(r["done"].double().mean()), float(gs.double().mean()), steps, mean_q
+
+
+def _eval_setup(model, env_config, grid_shift, device):
+    """What evaluate / prediction_smart do first: the model on ``device`` in eval mode -> the lattice size."""
+    model.to(device)
+    model.eval()
+    size = int(env_config["size"])
+    if int(grid_shift) != size // 2:
+        raise ValueError("grid_shift must be int(size/2)")
+    return size
+
+
 def evaluate(model, env, env_config, grid_shift, device, prediction_list_p_error, num_of_episodes=1,
              num_actions=3, epsilon=0.0, num_of_steps=50, plot_one_episode=False, minimum_nbr_of_qubit_errors=0,
              seed=0, chunk=1 << 16, round_like_reference=True):
@@ -220,11 +241,7 @@ def evaluate(model, env, env_config, grid_shift, device, prediction_list_p_error
     ``round_like_reference=False`` leaves steps (1 decimal upstream) and mean Q (3 decimals) unrounded."""
     # like upstream, `minimum_nbr_of_qubit_errors` is accepted and unused: the sampler is chosen by
     # env_config["min_qubit_errors"] (evaluation.py:51)
-    model.to(device)
-    model.eval()
-    size = int(env_config["size"])
-    if int(grid_shift) != size // 2:
-        raise ValueError("grid_shift must be int(size/2)")
+    size = _eval_setup(model, env_config, grid_shift, device)
     k = len(prediction_list_p_error)
     corrected, ground, steps_avg, mean_q = np.zeros(k), np.zeros(k), np.zeros(k), np.zeros(k)
     failed = []
@@ -236,20 +253,12 @@ def evaluate(model, env, env_config, grid_shift, device, prediction_list_p_error
         r = _greedy_episodes(envs, model, epsilon, num_of_steps, chunk)
         done = r["done"]
         gs = envs.evalGroundState().bool()
-        corrected[i] = float(done.double().mean())
-        ground[i] = float(gs.double().mean())
-        steps_avg[i] = float(r["n_steps"].double().mean())
-        mean_q[i] = float(r["q_sum"] / r["q_cnt"].clamp(min=1))
-        if round_like_reference:
-            steps_avg[i], mean_q[i] = np.round(steps_avg[i], 1), np.round(mean_q[i], 3)
         bad = (~done) | (~gs)
         if bool(bad.any()):
             fq = envs.getQubits()[bad].cpu().numpy()
             for a, b in zip(init_q[bad].cpu().numpy(), fq):
-                failed.append(a)
-                failed.append(b)
-        envs.check()
-        envs.close()
+                failed += [a, b]
+        corrected[i], ground[i], steps_avg[i], mean_q[i] = _close_p_error(envs, r, gs, round_like_reference)
     return corrected, ground, steps_avg, mean_q, failed
 
 
@@ -294,11 +303,7 @@ def prediction_smart(model, env, env_config, grid_shift, device, prediction_list
     -> (error_corrected_list, ground_state_list, average_number_of_steps_list, mean_q_list,
         number_of_failed_syndroms_list, N_fail, P_l_list, failed_syndromes) as upstream."""
     from math import comb
-    model.to(device)
-    model.eval()
-    size = int(env_config["size"])
-    if int(grid_shift) != size // 2:
-        raise ValueError("grid_shift must be int(size/2)")
+    size = _eval_setup(model, env_config, grid_shift, device)
     k = len(prediction_list_p_error)
     n_ep, q = int(num_of_episodes), int(nbr_of_qubit_errors)
     max_err = size * size
@@ -322,8 +327,8 @@ def prediction_smart(model, env, env_config, grid_shift, device, prediction_list
             raise RuntimeError("the sampler kept producing empty syndromes")
         flips = (qm != 0).reshape(n_ep, -1).sum(1)
         r = _greedy_episodes(envs, model, epsilon, num_of_steps, chunk)
-        done = r["done"].cpu().numpy()
-        gs = envs.evalGroundState().bool().cpu().numpy()
+        gs_dev = envs.evalGroundState().bool()
+        gs = gs_dev.cpu().numpy()
         inside = flips < max_err
         np.add.at(table[2], flips[inside & ~gs], 1)
         np.add.at(table[1], flips[inside & gs], 1)
@@ -332,12 +337,5 @@ def prediction_smart(model, env, env_config, grid_shift, device, prediction_list
         N_fail = float(n_fail.sum())
         nq = 2 * size * size
         P_l_list[i] = comb(nq, q) * float(p) ** q * (1 - float(p)) ** (nq - q) * N_fail / n_ep
-        corrected[i] = float(done.mean())
-        ground[i] = float(gs.mean())
-        steps_avg[i] = float(r["n_steps"].double().mean())
-        mean_q[i] = float(r["q_sum"] / r["q_cnt"].clamp(min=1))
-        if round_like_reference:
-            steps_avg[i], mean_q[i] = np.round(steps_avg[i], 1), np.round(mean_q[i], 3)
-        envs.check()
-        envs.close()
+        corrected[i], ground[i], steps_avg[i], mean_q[i] = _close_p_error(envs, r, gs_dev, round_like_reference)
     return corrected, ground, steps_avg, mean_q, table, N_fail, P_l_list, failed

@@ -12,8 +12,8 @@ import numpy as np
 import torch
 
 from . import _lib, wire
-from ._lib import _ptr, _stream, check
-from .envset import TransitionBlock
+from ._lib import Handle, _ptr, _stream, check, to_device
+from .transition import TransitionBlock
 
 MAX_BATCH = 4096
 
@@ -32,7 +32,7 @@ def block_capacity(d, nbytes):
     return lo
 
 
-class PrioritizedReplayMemory:
+class PrioritizedReplayMemory(Handle):
     """PrioritizedReplayMemory(memory_size, alpha) (ReplayMemory.py:45-75) held on ``device``.
 
     ``d``: lattice size of the records; ``seed``: key of the handle's own uniforms (RNG domain 5, DESIGN.md §4);
@@ -50,25 +50,11 @@ class PrioritizedReplayMemory:
             raise ValueError("the replay memory lives on a GPU (device='cuda[:k]')")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device() if torch.cuda.is_available() else 0)
-        h = C.c_void_p(None)
-        check(self._L.tq_replay_create(C.byref(h), self.size, self.memory_size, self.alpha, self.device.index,
+        self._h = C.c_void_p(None)
+        check(self._L.tq_replay_create(C.byref(self._h), self.size, self.memory_size, self.alpha, self.device.index,
                                        int(seed) & ((1 << 64) - 1), int(self.faithful)))
-        self._h = h
 
-    def _call(self, fn, *args):
-        with torch.cuda.device(self.device):
-            return check(fn(self._h, *args, _stream()))
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.tq_replay_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    _destroy = "tq_replay_destroy"
 
     # ---------------------------------------------------------------- ingest
     def save_block(self, block):
@@ -139,7 +125,7 @@ class PrioritizedReplayMemory:
     def get(self, indices):
         """Records at ``indices`` (int64 device tensor or sequence) -> dict of device tensors: state / next_state
         f32 (n,2,d,d), actions i64 (op - 1), reward f32, terminal bool, action i32 (n,4) (the raw [layer,row,col,op])."""
-        idx = torch.as_tensor(indices, dtype=torch.int64, device=self.device).contiguous()
+        idx = to_device(indices, torch.int64, self.device)
         out = self._batch_outputs(idx.numel())
         self._call(self._L.tq_replay_get, _ptr(idx), int(idx.numel()), _ptr(out["state"]), _ptr(out["next_state"]),
                    _ptr(out["actions"]), _ptr(out["reward"]), _ptr(out["terminal"]), _ptr(out["action"]))
@@ -147,10 +133,8 @@ class PrioritizedReplayMemory:
 
     # ---------------------------------------------------------------- sampling
     def _uniforms(self, u, n):
-        if u is None:
-            return None
-        u = torch.as_tensor(u, dtype=torch.float64, device=self.device).contiguous()
-        if u.numel() != n:
+        u = to_device(u, torch.float64, self.device)
+        if u is not None and u.numel() != n:
             raise ValueError("need one uniform per draw")
         return u
 
@@ -196,8 +180,8 @@ class PrioritizedReplayMemory:
     def update_priorities(self, indices, priorities):
         """priority_update on device tensors (Learner_mp.py:160-169 -> IO_mp.py): leaf = priority**alpha, last
         occurrence of an index wins."""
-        idx = torch.as_tensor(indices, dtype=torch.int64, device=self.device).contiguous().reshape(-1)
-        p = torch.as_tensor(priorities, device=self.device).to(torch.float64).contiguous().reshape(-1)
+        idx = to_device(indices, torch.int64, self.device).reshape(-1)
+        p = to_device(priorities, torch.float64, self.device).reshape(-1)
         if idx.numel() != p.numel():
             raise ValueError("indices and priorities differ in length")
         self._call(self._L.tq_replay_update, _ptr(idx), _ptr(p), int(idx.numel()))
