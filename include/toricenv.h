@@ -175,6 +175,25 @@ int tq_persp_write(tq_env* h, const int64_t* offsets, void* out, int32_t* positi
 int tq_persp_write_range(tq_env* h, const int64_t* offsets, int first, int count, void* out,
                          int32_t* positions, int64_t capacity, int dtype, void* stream);
 
+/* "That stack write is done", for a second stream, without a packet of its own.  An event recorded behind a kernel
+ * (hipEventRecord) is a barrier packet with a signal: ~3 us of stream time, and the next kernel of the stream starts
+ * 5-7 us later than it does behind a kernel (profiles/step_fixed_cost.txt).  The _signal variants bind a library-owned
+ * event to the write's own dispatch packet instead (the extended launch form of the HIP runtime with a stop event): the
+ * stream carries kernel after kernel, and tq_stream_wait_event(done, other_stream) orders another stream behind the
+ * write.  done == NULL: exactly tq_persp_write / tq_persp_write_range.  A stack written in several ranges passes the
+ * event with the LAST range (a stream runs its kernels in order).  Not for a stream that is being captured into a HIP
+ * graph (TQ_E_INVALID): a captured write is the plain tq_persp_write.  An event belongs to the device it was created
+ * on; it is signalled anew by every write it is passed to, and a wait sees the latest write enqueued before it (a wait
+ * for an event no write has taken yet returns at once).  create / destroy are set-up calls. */
+typedef struct tq_event tq_event;
+int tq_event_create(tq_event** out, int device);
+int tq_event_destroy(tq_event* ev);
+int tq_persp_write_signal(tq_env* h, const int64_t* offsets, void* out, int32_t* positions,
+                          int64_t capacity, int dtype, tq_event* done, void* stream);
+int tq_persp_write_range_signal(tq_env* h, const int64_t* offsets, int first, int count, void* out,
+                                int32_t* positions, int64_t capacity, int dtype, tq_event* done, void* stream);
+int tq_stream_wait_event(tq_event* ev, void* stream);
+
 /* Same two steps for a batch of syndromes that does not live in a handle (the learner's
  * predictMaxOptimized, util_learner.py:48-111): states = device u8[n,2,d,d]. */
 /* set-up: size the calling device's scratch for up to n_max states of size d (allocates, synchronises).  The

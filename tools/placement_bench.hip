@@ -98,7 +98,7 @@ int main(int argc, char** argv) {
     int32_t* counts; CK(hipMalloc(&counts, 4 * N + 64));
     int64_t* part; CK(hipMalloc(&part, 8 * ((N + 255) / 256)));
     int64_t* off; CK(hipMalloc(&off, 8 * (N + 2)));
-    int32_t* split; CK(hipMalloc(&split, 4 * 258));
+    int32_t* split; CK(hipMalloc(&split, 4 * 264));
     int* err; CK(hipMalloc(&err, 4)); CK(hipMemset(err, 0, 4));
     hipLaunchKernelGGL(k_counts, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, vp, counts, N, part);
     hipLaunchKernelGGL(tq::k_scan_final, dim3((unsigned)((N + tq::SCAN_CHUNK - 1) / tq::SCAN_CHUNK)), dim3(256), 0, 0, counts,

@@ -138,7 +138,7 @@ int run(int64_t N, double q) {
     int32_t* counts; CK(hipMalloc(&counts, 4 * N + 64));
     int64_t* part; CK(hipMalloc(&part, 8 * ((N + 255) / 256)));
     int64_t* off; CK(hipMalloc(&off, 8 * (N + 2)));
-    int32_t *split, *split2; CK(hipMalloc(&split, 4 * 258)); CK(hipMalloc(&split2, 4 * 258));
+    int32_t *split, *split2; CK(hipMalloc(&split, 4 * 264)); CK(hipMalloc(&split2, 4 * 264));
     int* err; CK(hipMalloc(&err, 4)); CK(hipMemset(err, 0, 4));
     hipLaunchKernelGGL(k_counts<D>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, vp, counts, N, part);
     hipLaunchKernelGGL(tq::k_scan_final, dim3((unsigned)((N + tq::SCAN_CHUNK - 1) / tq::SCAN_CHUNK)), dim3(256), 0, 0, counts,
@@ -154,7 +154,7 @@ int run(int64_t N, double q) {
         const int64_t ranges[][2] = {{0, 64}, {64, 192}, {64, 191}, {1, 129}, {128, 256}, {0, 63}, {0, 65}, {4096, 8192}, {16384, 32768}, {5, N}};
         for (auto& r : ranges) {
             if (r[1] > N) continue;
-            CK(hipMemset(split2, 0xff, 4 * 258));
+            CK(hipMemset(split2, 0xff, 4 * 264));
             hipLaunchKernelGGL(tq::k_split, dim3((256 + 1 + 3) / 4), dim3(256), 0, 0, (const int64_t*)off, r[0], r[1], split2, 8);
             CK(hipMemcpy(hs2, split2, 4 * 257, hipMemcpyDeviceToHost));
             int nbad = 0, first_bad = -1;

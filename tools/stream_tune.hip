@@ -206,7 +206,7 @@ void rebalance(Ctx& c, const std::vector<int64_t>& off_h) {
     constexpr int WV = NS + NPW + NP;
     const int64_t N = c.N, P = off_h[N];
     std::vector<double> share(256, 1.0 / 256);
-    int32_t* sp; CK(hipMalloc(&sp, 4 * 258));
+    int32_t* sp; CK(hipMalloc(&sp, 4 * 264));
     unsigned long long* st; CK(hipMalloc(&st, sizeof(unsigned long long) * 256 * WV * 4));
     for (int pass = 0; pass < 4; ++pass) {
         std::vector<int32_t> cut(257);
@@ -262,7 +262,7 @@ int run(int64_t N, double q, const char* tname) {
     int32_t* counts; CK(hipMalloc(&counts, 4 * N + 64));
     int64_t* part; CK(hipMalloc(&part, 8 * ((N + 255) / 256)));
     int64_t* off; CK(hipMalloc(&off, 8 * (N + 2)));
-    int32_t* split; CK(hipMalloc(&split, 4 * 258));
+    int32_t* split; CK(hipMalloc(&split, 4 * 264));
     int* err; CK(hipMalloc(&err, 4)); CK(hipMemset(err, 0, 4));
     hipLaunchKernelGGL(k_counts<D>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, vp, counts, N, part);
     hipLaunchKernelGGL(tq::k_scan_final, dim3((unsigned)((N + tq::SCAN_CHUNK - 1) / tq::SCAN_CHUNK)), dim3(256), 0, 0, counts,
@@ -401,7 +401,7 @@ int run_all(int64_t N, double q) {
     int32_t* counts; CK(hipMalloc(&counts, 4 * N + 64));
     int64_t* part; CK(hipMalloc(&part, 8 * ((N + 255) / 256)));
     int64_t* off; CK(hipMalloc(&off, 8 * (N + 2)));
-    int32_t* split; CK(hipMalloc(&split, 4 * 258));
+    int32_t* split; CK(hipMalloc(&split, 4 * 264));
     int* err; CK(hipMalloc(&err, 4)); CK(hipMemset(err, 0, 4));
     hipLaunchKernelGGL(k_counts<D>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, vp, counts, N, part);
     hipLaunchKernelGGL(tq::k_scan_final, dim3((unsigned)((N + tq::SCAN_CHUNK - 1) / tq::SCAN_CHUNK)), dim3(256), 0, 0, counts,

@@ -50,6 +50,11 @@ SYMBOLS = [
     ("tq_persp_count", _i, [_vp, _vp, _vp, _vp]),
     ("tq_persp_write", _i, [_vp, _vp, _vp, _vp, _i64, _i, _vp]),
     ("tq_persp_write_range", _i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _i, _vp]),
+    ("tq_event_create", _i, [C.POINTER(_vp), _i]),
+    ("tq_event_destroy", _i, [_vp]),
+    ("tq_persp_write_signal", _i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    ("tq_persp_write_range_signal", _i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _i, _vp, _vp]),
+    ("tq_stream_wait_event", _i, [_vp, _vp]),
     ("tq_states_reserve", _i, [_i, _i]),
     ("tq_states_persp_count", _i, [_i, _i, _vp, _vp, _vp, _vp]),
     ("tq_states_persp_write", _i, [_i, _i, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
@@ -164,6 +169,34 @@ class Handle:
     def close(self):
         if self._h is not None and self._h.value:
             getattr(self._L, self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class WriteEvent:
+    """A library-owned event that a stack write signals with its own dispatch (tq_persp_write_signal: no packet of its
+    own on the write's stream) and another stream waits for: ``EnvSet.writePerspectives(..., done=ev)``, then
+    ``ev.wait(stream)``."""
+
+    def __init__(self, device):
+        self.device = require_gpu(device)
+        self._L = load()
+        self._h = C.c_void_p(None)
+        check(self._L.tq_event_create(C.byref(self._h), self.device.index))
+
+    def wait(self, stream=None):
+        """Order ``stream`` (default: the current one) behind the last write this event was passed to."""
+        s = _stream() if stream is None else C.c_void_p(stream.cuda_stream)
+        check(self._L.tq_stream_wait_event(self._h, s))
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            self._L.tq_event_destroy(self._h)
             self._h = None
 
     def __del__(self):

@@ -11,6 +11,7 @@ gather.TransitionGather on N>1) -- the (transition, priority) pairs of Actor_mp.
 import numpy as np
 import torch
 
+from ._lib import WriteEvent
 from .policy import selectActionEnvSet
 
 
@@ -25,7 +26,8 @@ class ExploreLoop:
     network would read); step(t) = tq_actor_step with in-kernel selection (step, transition record into ``blocks``,
     auto-reset, counts); scan(t+1) = tq_persp_count into the other of two offsets rows.  The handle keeps two plane
     buffers and two cut-point tables in turn (include/toricenv.h, tq_actor_step), so the only ordering left to the
-    caller is: write(t) behind scan(t); step(t+1) behind write(t) -- two events per step.  With a Q-table in the loop
+    caller is: write(t) behind scan(t); step(t+1) behind write(t) -- two events per step, and the second one is signalled
+    by write(t)'s own dispatch (tq_persp_write_signal), so stream A carries kernel after kernel.  With a Q-table in the loop
     step(t) depends on the stack and the path is serial (run_actor).  ``overlap=False``: everything on stream A, in
     the reference's order.
 
@@ -55,7 +57,7 @@ class ExploreLoop:
         self.B = torch.cuda.Stream(device=self.dev) if overlap else self.A
         self.overlap = self.B is not self.A
         self.scanned = [torch.cuda.Event() for _ in range(2)]
-        self.written = [torch.cuda.Event() for _ in range(2)]
+        self.written = [WriteEvent(self.dev) for _ in range(2)] if self.overlap else [None, None]
         self.t = 0
         if self.overlap:
             self.B.wait_stream(self.A)                           # whatever set the lattices up
@@ -82,19 +84,19 @@ class ExploreLoop:
                 self.A.wait_event(self.scanned[k])
         if bracket is not None:
             bracket[0].record(self.A)
+        done = self.written[k]                                    # signalled by the write's (last) launch itself: no record on A
         if self.chunks == 1:
-            envs.writePerspectives(self.stack, self.positions, off)
+            envs.writePerspectives(self.stack, self.positions, off, done=done)
         else:
             per = envs.no_envs // self.chunks
             for c in range(self.chunks):                          # a consumer would read the buffer between two ranges
-                envs.writePerspectives(self.stack, self.positions, off, first=c * per, count=per)
+                envs.writePerspectives(self.stack, self.positions, off, first=c * per, count=per,
+                                       done=done if c == self.chunks - 1 else None)
         if bracket is not None:
             bracket[1].record(self.A)
-        if self.overlap:
-            self.written[k].record(self.A)
         with torch.cuda.stream(self.B):
             if self.overlap and t > 0:
-                self.B.wait_event(self.written[k ^ 1])            # write(t-1) read the plane buffer this step writes
+                self.written[k ^ 1].wait(self.B)                  # write(t-1) read the plane buffer this step writes
             blk = self.blocks[(t // self.flush) % len(self.blocks)] if self.blocks else None
             envs.actorStep(None, block=blk, slot=t % self.flush, want_actions=True)
             if blk is not None and (t + 1) % self.flush == 0:

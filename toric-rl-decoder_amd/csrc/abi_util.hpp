@@ -5,6 +5,7 @@
 #include "toricenv.h"
 
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdarg.h>
 #include <stdio.h>
 
@@ -54,6 +55,15 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 template <typename... P, typename... A>
 __forceinline__ int launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t stream, A&&... args) {
     hipLaunchKernelGGL(kernel, grid, block, 0, stream, static_cast<P>(args)...);
+    KCHECK();
+    return TQ_OK;
+}
+// The same with `done` (may be NULL) signalled by the kernel's own dispatch packet when the kernel has finished -- no
+// barrier packet behind it, as hipEventRecord would enqueue.  Never on a stream that is being captured.
+template <typename... P, typename... A>
+__forceinline__ int launch_signal(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t stream, hipEvent_t done, A&&... args) {
+    if (!done) return launch(kernel, grid, block, stream, args...);
+    hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, nullptr, done, 0, static_cast<P>(args)...);
     KCHECK();
     return TQ_OK;
 }

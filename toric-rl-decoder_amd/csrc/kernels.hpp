@@ -454,7 +454,10 @@ __global__ __launch_bounds__(256) void k_scan_partials(const int32_t* __restrict
 // `split` (may be NULL): cut points of the batch into G = 1 << LG parts of equal perspective count for the
 // stack write (stream_write.hpp): split[k] = first lattice e with offsets[e] >= (P * k) >> LG, k = 0..G.
 // A by-product of the scan: every thread knows the offsets around its eight lattices, the workgroup sums all
-// level-1 partials for P, and the thread whose interval holds a cut point writes it.
+// level-1 partials for P, and the thread whose interval holds a cut point writes it.  Behind the G + 1 cut points the
+// table carries a header of SPLIT_HEADER words -- P (low, high) and N -- by which the stack write tells that a table
+// belongs to the offsets it was handed (a table is matched to an offsets POINTER, whose contents the caller owns).
+constexpr int SPLIT_HEADER = 3;
 __global__ __launch_bounds__(256) void k_scan_final(const int32_t* __restrict__ counts, const int64_t* __restrict__ partial,
                                                     int64_t* __restrict__ offsets, int32_t* __restrict__ counts_out,
                                                     int64_t N, int32_t* __restrict__ split, int LG) {
@@ -516,6 +519,9 @@ __global__ __launch_bounds__(256) void k_scan_final(const int32_t* __restrict__ 
     if (split) {
         const int64_t total = total_s;
         const int G = 1 << LG;
+        if (blockIdx.x == 0 && tid == 0) {
+            split[G + 1] = (int32_t)(uint32_t)total; split[G + 2] = (int32_t)(uint32_t)((uint64_t)total >> 32); split[G + 3] = (int32_t)N;
+        }
         if (total == 0) {                                     // empty stack: any valid table will do
             if (blockIdx.x == 0) for (int k = tid; k <= G; k += 256) split[k] = 0;
         } else {

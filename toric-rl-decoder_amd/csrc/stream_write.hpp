@@ -195,7 +195,8 @@ __global__ __launch_bounds__(64 * (NS + NPW + NP)) void k_persp_stream(const uin
     const int RR = (1 << lg) / (int)gridDim.x;
     // a small stack is not bound by the stores: equal shares, and no counters (their atomic's round trip across the XCDs is
     // ~3 us at the start of a launch: nothing beside 280 us, a fifth of a 15 us launch)
-    if (!slots || bias >= RR || (offsets[e_end] - offsets[e_begin]) * (int64_t)(NQ * sizeof(OutT)) < (int64_t)(64 << 20)) bias = 0;
+    const int64_t p_tab = offsets[e_end] - offsets[e_begin];  // perspectives of the whole stack
+    if (!slots || bias >= RR || p_tab * (int64_t)(NQ * sizeof(OutT)) < (int64_t)(64 << 20)) bias = 0;
     const bool take = bias > 0;
     __shared__ int slot_s[2];
     if (threadIdx.x == 0) {
@@ -233,8 +234,19 @@ __global__ __launch_bounds__(64 * (NS + NPW + NP)) void k_persp_stream(const uin
     }
     const int f_lo = slot_s[1] * 2 * RR + (slot_s[0] ? 0 : RR + bias);
     const int f_hi = f_lo + (slot_s[0] ? RR + bias : RR - bias);
-    int64_t e_lo, e_hi;
+    // A table is followed only if it is the table of THESE offsets over THIS lattice range: its header (k_scan_final) holds
+    // the stack's perspective count and the last lattice, and a scan covers [0, N].  The handle matches tables to offsets
+    // POINTERS; a caller who refilled a scanned array hands in a table of another stack -- all zero, say, which would leave
+    // the stack unwritten with nothing latched.  Such a table is not followed: the workgroups find their cut points
+    // themselves.  (Loads beside the two above: nothing is added to the start of a launch.)
+    bool by_tab = false;
     if (split) {
+        const int G = 1 << lg;
+        const int64_t t_all = (int64_t)(((uint64_t)(uint32_t)split[G + 2] << 32) | (uint32_t)split[G + 1]);
+        by_tab = t_all == p_tab && e_begin == 0 && (int64_t)split[G + 3] == e_end;
+    }
+    int64_t e_lo, e_hi;
+    if (by_tab) {
         e_lo = split[f_lo]; e_hi = split[f_hi];
     } else {
         __shared__ int64_t cut[2];

@@ -25,7 +25,7 @@ struct DeviceCtx {
 };
 constexpr int SPLIT_MAX = 256;       // persistent workgroups of the stack write: one per CU of an MI355X
 constexpr int SPLIT_LG = 13;         // the scan's table cuts the stack into 1 << SPLIT_LG fine parts: 32 per workgroup
-constexpr int SPLIT_ENTRIES = (1 << SPLIT_LG) + 1;
+constexpr int SPLIT_ENTRIES = (1 << SPLIT_LG) + 1;   // + SPLIT_HEADER words behind them (k_scan_final): allocated as SPLIT_ENTRIES + 3
 constexpr int N_SLOT_SETS = 8;       // sets of slot counters of the stack write, used in turn
 // Fine parts (of 32) that the workgroup of an odd XCD hands to its even neighbour (stream_write.hpp: the odd XCDs of an
 // MI355X store ~20 % slower; sweep in profiles/r04_xcd_bias_sweep.txt).  tq_set_xcd_bias / TORICENV_XCD_BIAS = 0..16.
@@ -117,28 +117,32 @@ struct StreamCfg {
 template <int D, typename OutT>
 int launch_persp_write_t(const uint64_t* vp, int64_t n, const int64_t* offsets, void* out, int32_t* pos,
                          int64_t capacity, int* err, hipStream_t stream, int64_t first, int64_t count,
-                         const int32_t* split, unsigned int* slots, int bias) {
+                         const int32_t* split, unsigned int* slots, int bias, hipEvent_t done) {
     using C = StreamCfg<D, (int)sizeof(OutT)>;
     // a workgroup's part of the stack is addressed with 32-bit element offsets
     if ((double)count * (2.0 * D * D) * (2.0 * D * D) / SPLIT_MAX * 1.5 > 2.0e9)    // (the largest share is 1.5 of the mean)
         return fail(TQ_E_INVALID, "lattice range too large for one stack write (%lld lattices of d=%d)", (long long)count, D);
-    return launch(tq::k_persp_stream<D, OutT, C::NS, C::NP, C::CPW, C::RB, C::RP, false, C::NPW>, dim3(SPLIT_MAX),
-                  dim3(64 * (C::NS + C::NPW + C::NP)), stream, vp, n, offsets, out, pos, capacity, err, first, first + count, split,
-                  SPLIT_LG, (D >= 7 && sizeof(OutT) >= 2) ? bias : 0, slots, nullptr);
+    return launch_signal(tq::k_persp_stream<D, OutT, C::NS, C::NP, C::CPW, C::RB, C::RP, false, C::NPW>, dim3(SPLIT_MAX),
+                         dim3(64 * (C::NS + C::NPW + C::NP)), stream, done, vp, n, offsets, out, pos, capacity, err, first,
+                         first + count, split, SPLIT_LG, (D >= 7 && sizeof(OutT) >= 2) ? bias : 0, slots, nullptr);
 }
 
 // split == nullptr: the cut points did not come with the scan of these offsets (a lattice sub-range, or offsets from
-// elsewhere): every workgroup of the write finds its own two (find_cut)
+// elsewhere): every workgroup of the write finds its own two (find_cut).  done (may be NULL): an event the launch signals
+// when it has finished (launch_signal); with no lattice to write there is no launch, and the event is recorded plainly.
 template <int D>
 int launch_persp_write(const uint64_t* vp, int64_t n, const int64_t* offsets, void* out, int32_t* pos,
                        int64_t capacity, int dtype, int* err, hipStream_t stream, int64_t first, int64_t count,
-                       const int32_t* split, unsigned int* slots = nullptr, int bias = 0) {
-    if (count == 0) return TQ_OK;
+                       const int32_t* split, unsigned int* slots = nullptr, int bias = 0, hipEvent_t done = nullptr) {
+    if (count == 0) {
+        if (done) HIPCHECK(hipEventRecord(done, stream));
+        return TQ_OK;
+    }
     switch (dtype) {
-        case TQ_F32: return launch_persp_write_t<D, float>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias);
-        case TQ_F16: return launch_persp_write_t<D, __half>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias);
-        case TQ_BF16: return launch_persp_write_t<D, tq::bf16_t>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias);
-        case TQ_U8: return launch_persp_write_t<D, uint8_t>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias);
+        case TQ_F32: return launch_persp_write_t<D, float>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias, done);
+        case TQ_F16: return launch_persp_write_t<D, __half>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias, done);
+        case TQ_BF16: return launch_persp_write_t<D, tq::bf16_t>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias, done);
+        case TQ_U8: return launch_persp_write_t<D, uint8_t>(vp, n, offsets, out, pos, capacity, err, stream, first, count, split, slots, bias, done);
         default: return fail(TQ_E_INVALID, "unknown dtype %d", dtype);
     }
 }
@@ -406,14 +410,56 @@ int tq_persp_count(tq_env* h, int32_t* counts, int64_t* offsets, void* stream_) 
     return TQ_OK;
 }
 
-int tq_persp_write_range(tq_env* h, const int64_t* offsets, int first, int count, void* out, int32_t* positions,
-                         int64_t capacity, int dtype, void* stream_) {
+struct tq_event {          // an event the library owns: signalled by a stack write's own dispatch (tq_persp_write_signal)
+    int device;
+    hipEvent_t ev;
+};
+
+int tq_event_create(tq_event** out, int device) {
+    if (!out) return fail(TQ_E_INVALID, "out is NULL");
+    *out = nullptr;
+    if (int rc = valid_device(device)) return rc;
+    DeviceGuard guard;
+    if (int rc = guard.enter_device(device)) return rc;
+    hipEvent_t ev;
+    HIPCHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    tq_event* e = new (std::nothrow) tq_event{device, ev};
+    if (!e) { (void)hipEventDestroy(ev); return fail(TQ_E_INVALID, "out of host memory"); }
+    *out = e;
+    return TQ_OK;
+}
+
+int tq_event_destroy(tq_event* ev) {
+    if (!ev) return TQ_OK;
+    DeviceGuard guard;
+    (void)guard.enter_device(ev->device);
+    (void)hipEventDestroy(ev->ev);
+    delete ev;
+    return TQ_OK;
+}
+
+int tq_stream_wait_event(tq_event* ev, void* stream_) {
+    DeviceGuard guard;
+    if (int rc = guard.enter(ev)) return rc;
+    HIPCHECK(hipStreamWaitEvent((hipStream_t)stream_, ev->ev, 0));
+    return TQ_OK;
+}
+
+int tq_persp_write_range_signal(tq_env* h, const int64_t* offsets, int first, int count, void* out, int32_t* positions,
+                                int64_t capacity, int dtype, tq_event* done, void* stream_) {
     HANDLE(h);
     if (!offsets || !out) return fail(TQ_E_INVALID, "offsets / out is NULL");
     if (capacity < 0) return fail(TQ_E_INVALID, "negative capacity");
     if (first < 0 || count < 0 || (int64_t)first + count > h->n) return fail(TQ_E_INVALID, "lattice range outside [0, n_envs)");
     REQUIRE_ALIGNED16(out, "out");
     REQUIRE_ALIGNED16(positions, "positions");
+    if (done) {
+        if (done->device != h->device) return fail(TQ_E_INVALID, "the event belongs to device %d, the handle to %d", done->device, h->device);
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        HIPCHECK(hipStreamIsCapturing(stream, &cap));
+        if (cap != hipStreamCaptureStatusNone)
+            return fail(TQ_E_INVALID, "tq_persp_write_signal on a capturing stream: capture the plain tq_persp_write");
+    }
     const uint64_t* vp = h->planes + (size_t)tq::PL_V * h->w * h->n;
     // the cut points of the whole batch came with the scan of these very offsets; for a lattice sub-range, or offsets
     // from elsewhere, the workgroups find theirs themselves
@@ -425,14 +471,25 @@ int tq_persp_write_range(tq_env* h, const int64_t* offsets, int first, int count
     unsigned int* slots = h->slots + tq::STREAM_SLOT_WORDS * (h->write_seq++ % N_SLOT_SETS);
     return by_size(h->d, [&](auto D) {
         return launch_persp_write<D()>(vp, h->n, offsets, out, positions, capacity, dtype, h->err, stream, first, count, split,
-                                       slots, h->xcd_bias >= 0 ? h->xcd_bias : xcd_bias());
+                                       slots, h->xcd_bias >= 0 ? h->xcd_bias : xcd_bias(), done ? done->ev : nullptr);
     });
+}
+
+int tq_persp_write_range(tq_env* h, const int64_t* offsets, int first, int count, void* out, int32_t* positions,
+                         int64_t capacity, int dtype, void* stream_) {
+    return tq_persp_write_range_signal(h, offsets, first, count, out, positions, capacity, dtype, nullptr, stream_);
+}
+
+int tq_persp_write_signal(tq_env* h, const int64_t* offsets, void* out, int32_t* positions, int64_t capacity,
+                          int dtype, tq_event* done, void* stream_) {
+    if (!h) return fail(TQ_E_INVALID, "NULL handle");
+    return tq_persp_write_range_signal(h, offsets, 0, h->n, out, positions, capacity, dtype, done, stream_);
 }
 
 int tq_persp_write(tq_env* h, const int64_t* offsets, void* out, int32_t* positions, int64_t capacity,
                    int dtype, void* stream_) {
     if (!h) return fail(TQ_E_INVALID, "NULL handle");
-    return tq_persp_write_range(h, offsets, 0, h->n, out, positions, capacity, dtype, stream_);
+    return tq_persp_write_range_signal(h, offsets, 0, h->n, out, positions, capacity, dtype, nullptr, stream_);
 }
 
 // ---- stateless variants (states outside a handle) -------------------------------------------

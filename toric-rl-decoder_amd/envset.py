@@ -265,11 +265,12 @@ class EnvSet(Handle):
         self._call(self._L.tq_persp_count, _ptr(self._counts), _ptr(self._offsets))
         return self._counts, self._offsets
 
-    def writePerspectives(self, out, positions=None, offsets=None, first=0, count=None):
+    def writePerspectives(self, out, positions=None, offsets=None, first=0, count=None, done=None):
         """Write the stack for ``offsets`` (default: the last perspectiveCounts) into the
         caller's tensor ``out`` (capacity = out.shape[0] perspectives).  No synchronisation.
         ``first`` / ``count``: only the lattices [first, first+count), their first perspective at
-        out[0] -- for consumers that walk the batch in chunks."""
+        out[0] -- for consumers that walk the batch in chunks.
+        ``done``: a _lib.WriteEvent the write's own dispatch signals when it has finished (not under graph capture)."""
         if out.dtype not in _DTYPES or not out.is_contiguous():
             raise ValueError("out must be a contiguous float32/float16/bfloat16/uint8 tensor")
         nq = 2 * self.size * self.size
@@ -277,10 +278,14 @@ class EnvSet(Handle):
         if positions is not None and (positions.dtype != torch.int32 or positions.numel() < 3 * cap):
             raise ValueError("positions must be int32 with at least 3*capacity elements")
         off = self._offsets if offsets is None else offsets
-        if first == 0 and count is None:
+        whole = first == 0 and count is None
+        count = self.no_envs - int(first) if count is None else int(count)
+        if done is not None:
+            self._call(self._L.tq_persp_write_range_signal, _ptr(off), int(first), count, _ptr(out), _ptr(positions), cap,
+                       _DTYPES[out.dtype], done._h)
+        elif whole:
             self._call(self._L.tq_persp_write, _ptr(off), _ptr(out), _ptr(positions), cap, _DTYPES[out.dtype])
         else:
-            count = self.no_envs - int(first) if count is None else int(count)
             self._call(self._L.tq_persp_write_range, _ptr(off), int(first), count, _ptr(out), _ptr(positions), cap,
                        _DTYPES[out.dtype])
         self._positions = positions
