@@ -233,6 +233,17 @@ int tq_states_check(void* stream);
 int tq_segment_max(const float* q_table, const int64_t* offsets, int n, const int32_t* largest,
                    float* out, void* stream);
 
+/* The learner's TD targets behind the forward of the next states' perspectives (Learner_mp.py:146-151) in one launch:
+ *   y[i] = clamp(rewards[i] + (terminals[i] ? 0 : 1) * discount * m[i], lo, hi)
+ * with m[i] = tq_segment_max's result WITH the reference's zero padding: 0 for an empty slice, max(max_q, 0) for a slice
+ * shorter than the batch's longest, max_q for one as long.  The longest slice is found on the device inside the call (no
+ * `largest` argument, no host read).  q_table f32[P,3] (may be NULL when P = 0), offsets i64[n+1], rewards f32[n],
+ * terminals u8[n] (0/1, a torch.bool tensor) -> y f32[n].  f32 arithmetic with the roundings of the torch expression
+ * reward + (~terminal).float() * discount * target -- ((1 - t) * discount) * m, then + reward, then the clamp, nothing
+ * contracted -- so y is bit-identical to that expression on the same inputs. */
+int tq_td_target(const float* q_table, const int64_t* offsets, int n, const float* rewards,
+                 const uint8_t* terminals, float discount, float lo, float hi, float* y, void* stream);
+
 /* generateTransitionParallel (util_actor.py:223-264) for the last tq_step: perspective of the
  * pre-step and post-step syndrome centred on the acted qubit (rotated for layer 1), action
  * rewritten to (layer, gs, gs, op).  Outputs (any may be NULL): persp u8[N,2,d,d],
@@ -314,8 +325,9 @@ int tq_check(tq_env* h, void* stream);
  *    everything else only enqueues kernels.
  *  - indices are int64 record indices (leaf numbers); uniforms / priorities / weights / tree values are f64.
  *  - errors seen on the device are latched and reported by tq_replay_check: TQ_E_CAPACITY (a sample of more records
- *    than are filled), TQ_E_INDEX (an index outside [0, filled), or a draw that ended on an unfilled leaf).  Nothing
- *    outside the filled records is ever read. */
+ *    than are filled), TQ_E_INDEX (an index outside [0, filled), or a draw that ended on an unfilled leaf), and what the
+ *    stack writer of tq_replay_next_persp_write latches: TQ_E_CAPACITY (stack capacity exceeded), TQ_E_INVALID (offsets
+ *    that are not the scan of these records' counts).  Nothing outside the filled records is ever read. */
 typedef struct tq_replay tq_replay;
 
 /* PrioritizedReplayMemory(memory_size = capacity, alpha) for records of lattice size d; capacity 1..2^26, alpha >= 0.
@@ -341,6 +353,21 @@ int tq_replay_sample(tq_replay* r, int batch, double beta, const double* uniform
  * actions_idx i64[n] (op - 1), rewards f32[n], terminals u8[n] (0/1), and the raw actions i32[n,4]. */
 int tq_replay_get(tq_replay* r, const int64_t* indices, int n, float* state, float* next_state, int64_t* actions_idx,
                   float* rewards, uint8_t* terminals, int32_t* actions, void* stream);
+/* The learner's target side straight from the ring (predictMaxOptimized's generatePerspectiveBatch on the batch's
+ * next_state, util_learner.py:48-111, without expanding the records first): the two steps of tq_states_persp_count /
+ * tq_states_persp_write for the NEXT-state syndromes of the records at indices[0..n), n in 1..4096, whose packed planes
+ * are what the stack writer reads.  counts i32[n] (may be NULL), offsets i64[n+1]; then out[P,2,d,d] of `dtype`,
+ * positions i32[P,3] (may be NULL), capacity in perspectives; alignment as for tq_persp_write.  A count depends on the
+ * syndrome alone: a record with an empty next syndrome counts 0 whatever its terminal byte says.  An index outside
+ * [0, filled) reads nothing, counts 0 and latches TQ_E_INDEX.  The write gathers the planes again, so a count / write
+ * pair shares nothing but the handle's scratch (sized for 4096 records by tq_replay_create: no reserve call, no
+ * allocation here), and it checks `offsets` on the device as tq_persp_write does: offsets that are not the scan of these
+ * records' counts are refused (nothing stored outside [0, min(P, capacity)) perspectives, TQ_E_INVALID latched); lattices
+ * that would overflow `capacity` are skipped and TQ_E_CAPACITY is latched (tq_replay_check reports both). */
+int tq_replay_next_persp_count(tq_replay* r, const int64_t* indices, int n, int32_t* counts, int64_t* offsets,
+                               void* stream);
+int tq_replay_next_persp_write(tq_replay* r, const int64_t* indices, int n, const int64_t* offsets, void* out,
+                               int32_t* positions, int64_t capacity, int dtype, void* stream);
 /* priority_update(indices, priorities) (ReplayMemory.py:126-133): leaf = pow(p, alpha); of an index listed twice the
  * last occurrence wins. */
 int tq_replay_update(tq_replay* r, const int64_t* indices, const double* priorities, int n, void* stream);

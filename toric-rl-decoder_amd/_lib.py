@@ -62,6 +62,7 @@ SYMBOLS = [
     ("tq_states_select_action", _i, [_i, _vp, _vp, _vp, _vp, _u64, _u64, _i64, _vp, _vp, _vp]),
     ("tq_states_check", _i, [_vp]),
     ("tq_segment_max", _i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    ("tq_td_target", _i, [_vp, _vp, _i, _vp, _vp, C.c_float, C.c_float, C.c_float, _vp, _vp]),
     ("tq_transition_write", _i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     ("tq_states_transition", _i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tq_transition_block_bytes", _i64, [_i, _i64]),
@@ -75,6 +76,8 @@ SYMBOLS = [
     ("tq_replay_filled", _i64, [_vp, _vp]),
     ("tq_replay_sample", _i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tq_replay_get", _i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tq_replay_next_persp_count", _i, [_vp, _vp, _i, _vp, _vp, _vp]),
+    ("tq_replay_next_persp_write", _i, [_vp, _vp, _i, _vp, _vp, _vp, _i64, _i, _vp]),
     ("tq_replay_update", _i, [_vp, _vp, _vp, _i, _vp]),
     ("tq_replay_reset_alpha", _i, [_vp, _d, _vp]),
     ("tq_replay_leaves", _i, [_vp, _vp, _vp]),

@@ -2,6 +2,7 @@
 // after launch_scan, which the compaction of tq_replay_save_block shares with the environment).
 #pragma once
 #include <math.h>
+#include <stddef.h>
 
 #include <new>
 
@@ -19,6 +20,8 @@ struct tq_replay {                         // made by `new tq_replay()`: every m
     tq::ReplayDev* st;
     unsigned long long* stamp;             // u64[cap], last-wins stamps of the scatter update
     int32_t* flags; int64_t* partial; int64_t* offsets; int64_t scratch_cap;   // compaction scratch of save_block
+    uint64_t* nplanes;                     // u64[2][w][RP_MAX_BATCH]: next-state planes of a batch (tq_replay_next_persp_*)
+    int32_t* ncounts; int64_t* npartial;   // their perspective counts and the level-1 sums of the scan
     DeviceBuffers mem;                     // owns every device pointer above
 };
 
@@ -33,6 +36,7 @@ int replay_latch(int flag) {
     if (flag & tq::RP_ERR_INDEX) return fail(TQ_E_INDEX, "replay: an index outside [0, filled) was given");
     return TQ_OK;
 }
+static_assert(offsetof(tq::ReplayDev, werr) == offsetof(tq::ReplayDev, err) + sizeof(int), "tq_replay_check reads the two latches as one");
 #define RHANDLE(r)                                                \
     DeviceGuard _guard;                                           \
     if (!(r)) return fail(TQ_E_INVALID, "NULL replay handle");    \
@@ -57,6 +61,20 @@ int replay_update(tq_replay* r, const int64_t* idx, const double* p, int64_t n, 
     KCHECK();
     if (n * 64 >= r->cap) return replay_rebuild_all(r, stream);
     return launch(tq::k_replay_paths, dim3(1), dim3(1024), stream, idx, n, r->tree, r->L, r->st);
+}
+
+// the next-state planes of the records at indices[0..n) into the handle's scratch; with_counts: their perspective
+// counts and level-1 sums too
+template <int D>
+int replay_next_planes(tq_replay* r, const int64_t* indices, int n, bool with_counts, hipStream_t stream) {
+    return launch(tq::k_replay_next_planes<D>, dim3(grid1(n).x, tq::Lat<D>::W), dim3(BLOCK_1D), stream,
+                  tq::ring_view(r->ring, r->w, r->cap), indices, n, r->st, r->nplanes, with_counts ? r->ncounts : nullptr,
+                  r->npartial);
+}
+int replay_batch_ok(const int64_t* indices, int n) {
+    if (!indices) return fail(TQ_E_INVALID, "indices is NULL");
+    if (n < 1 || n > tq::RP_MAX_BATCH) return fail(TQ_E_INVALID, "n must be in 1..%d (got %d)", tq::RP_MAX_BATCH, n);
+    return TQ_OK;
 }
 }  // namespace
 
@@ -84,6 +102,9 @@ int tq_replay_create(tq_replay** out, int d, int64_t capacity, double alpha, int
     r->mem.zeroed(&r->ring, (size_t)tq::ring_bytes(r->w, capacity));
     r->mem.zeroed(&r->st, sizeof(tq::ReplayDev));
     r->mem.zeroed(&r->stamp, (size_t)capacity * sizeof(unsigned long long));
+    r->mem.zeroed(&r->nplanes, 2 * (size_t)r->w * tq::RP_MAX_BATCH * sizeof(uint64_t));
+    r->mem.zeroed(&r->ncounts, (size_t)tq::RP_MAX_BATCH * 4 + 32);          // +32: int4 tail loads of the scan stay in bounds
+    r->mem.zeroed(&r->npartial, (size_t)(tq::RP_MAX_BATCH / tq::PART_BLOCK) * 8);
     hipError_t e = r->mem.err;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) { tq_replay_destroy(r); return fail(TQ_E_HIP, "replay allocation failed: %s", hipGetErrorString(e)); }
@@ -176,6 +197,44 @@ int tq_replay_sample(tq_replay* r, int batch, double beta, const double* uniform
     return TQ_OK;
 }
 
+int tq_replay_next_persp_count(tq_replay* r, const int64_t* indices, int n, int32_t* counts, int64_t* offsets, void* stream_) {
+    RHANDLE(r);
+    if (int rc = replay_batch_ok(indices, n)) return rc;
+    if (!offsets) return fail(TQ_E_INVALID, "offsets is NULL");
+    REQUIRE_ALIGNED16(offsets, "offsets");
+    REQUIRE_ALIGNED16(counts, "counts");
+    if (int rc = by_size(r->d, [&](auto D) { return replay_next_planes<D()>(r, indices, n, true, stream); })) return rc;
+    // no cut-point table: the workgroups of the write find their cut points themselves, as for states outside a handle
+    return launch_scan(r->ncounts, r->npartial, true, offsets, counts, n, stream, nullptr);
+}
+
+// The planes are gathered again (as tq_states_persp_write packs again): a count / write pair shares nothing but the
+// scratch, and the writer checks the offsets against the planes it is given.
+int tq_replay_next_persp_write(tq_replay* r, const int64_t* indices, int n, const int64_t* offsets, void* out,
+                               int32_t* positions, int64_t capacity, int dtype, void* stream_) {
+    RHANDLE(r);
+    if (int rc = replay_batch_ok(indices, n)) return rc;
+    if (!offsets || !out) return fail(TQ_E_INVALID, "offsets / out is NULL");
+    if (capacity < 0) return fail(TQ_E_INVALID, "negative capacity");
+    REQUIRE_ALIGNED16(out, "out");
+    REQUIRE_ALIGNED16(positions, "positions");
+    return by_size(r->d, [&](auto D) {
+        if (int rc = replay_next_planes<D()>(r, indices, n, false, stream)) return rc;
+        return launch_persp_write<D()>(r->nplanes, n, offsets, out, positions, capacity, dtype, &r->st->werr, stream, 0, n, nullptr);
+    });
+}
+
+int tq_td_target(const float* q_table, const int64_t* offsets, int n, const float* rewards, const uint8_t* terminals,
+                 float discount, float lo, float hi, float* y, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (n <= 0 || !offsets || !rewards || !terminals || !y) return fail(TQ_E_INVALID, "bad n / offsets / rewards / terminals / y");
+    if (!(lo <= hi)) return fail(TQ_E_INVALID, "td target: lo must be <= hi");
+    // one wavefront per state, at most one workgroup per CU of an MI355X: each finds the longest slice for itself
+    const unsigned blocks = (unsigned)(((int64_t)n + 3) / 4);
+    return launch(tq::k_td_target, dim3(blocks < 256u ? blocks : 256u), dim3(256), stream, q_table, offsets, rewards, terminals,
+                  discount, lo, hi, y, n);
+}
+
 int tq_replay_update(tq_replay* r, const int64_t* indices, const double* priorities, int n, void* stream_) {
     RHANDLE(r);
     if (n < 0 || (n > 0 && (!indices || !priorities))) return fail(TQ_E_INVALID, "bad indices / priorities / n");
@@ -213,9 +272,12 @@ int tq_replay_tree(tq_replay* r, double* out, void* stream_) {
 
 int tq_replay_check(tq_replay* r, void* stream_) {
     RHANDLE(r);
-    int flag;
-    if (int rc = read_latch(&r->st->err, stream, &flag)) return rc;
-    return replay_latch(flag);
+    int flags[2] = {0, 0};                                   // the replay kernels' latch, the stack writer's
+    HIPCHECK(hipMemcpyAsync(flags, &r->st->err, sizeof(flags), hipMemcpyDeviceToHost, stream));
+    HIPCHECK(hipStreamSynchronize(stream));
+    if (flags[0] | flags[1]) HIPCHECK(hipMemsetAsync(&r->st->err, 0, sizeof(flags), stream));
+    if (int rc = replay_latch(flags[0])) return rc;
+    return decode_latch(flags[1]);
 }
 
 }  // extern "C"

@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "env_step.hpp"
+#include "td_target.hpp"
 
 namespace tq {
 
@@ -694,6 +695,42 @@ __global__ __launch_bounds__(256) void k_segment_max(const float* __restrict__ q
     if (cnt == 0) best = 0.f;
     else if (largest && cnt < *largest) best = fmaxf(best, 0.f);
     if (lane == 0) out[e] = best;
+}
+
+// The learner's TD targets (Learner_mp.py:146-151 behind the forward of the next states' perspectives): k_segment_max
+// with the reference's zero padding, then y = clamp(reward + (1 - terminal) * discount * max, lo, hi) in one launch
+// (td_target.hpp has the arithmetic).  The padding needs the longest slice of the batch: every workgroup finds it for
+// itself from the offsets (n + 1 cached loads per workgroup -- no second launch, no word shared between workgroups).
+// One wavefront per state, the workgroups striding over the states.
+__global__ __launch_bounds__(256) void k_td_target(const float* __restrict__ q, const int64_t* __restrict__ offsets,
+                                                   const float* __restrict__ rewards, const uint8_t* __restrict__ terminals,
+                                                   float discount, float lo, float hi, float* __restrict__ y, int64_t n) {
+    __shared__ int64_t wmax[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int64_t longest = 0;
+    for (int64_t i = threadIdx.x; i < n; i += 256) {
+        const int64_t c = offsets[i + 1] - offsets[i];
+        longest = c > longest ? c : longest;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int64_t t = __shfl_xor(longest, o, 64);
+        longest = t > longest ? t : longest;
+    }
+    if (lane == 0) wmax[wave] = longest;
+    __syncthreads();
+    longest = wmax[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) longest = wmax[w] > longest ? wmax[w] : longest;
+    for (int64_t e = (int64_t)blockIdx.x * 4 + wave; e < n; e += (int64_t)gridDim.x * 4) {
+        const int64_t first = offsets[e];
+        const int64_t cnt = offsets[e + 1] - first;
+        float best = -__builtin_inff();
+        for (int64_t k = lane; k < 3 * cnt; k += 64) best = fmaxf(best, q[3 * first + k]);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+        if (lane == 0) y[e] = td_target_value(rewards[e], terminals[e], discount, td_next_max(best, cnt, longest), lo, hi);
+    }
 }
 
 }  // namespace tq

@@ -13,7 +13,9 @@
 //   * scatter update with last-wins (k_replay_stamp / k_replay_scatter) and the rebuild of the touched paths
 //     (k_replay_paths, one workgroup, level by level);
 //   * k_replay_sample: B sequential draws in ONE workgroup, the reference's sample loop with its += diff semantics;
-//   * k_replay_gather<D>: records at given indices -> the learner's batch tensors (dataToBatch, util_learner.py:7-46).
+//   * k_replay_gather<D>: records at given indices -> the learner's batch tensors (dataToBatch, util_learner.py:7-46);
+//   * k_replay_next_planes<D>: the next-state planes of the records at given indices, as they are, into the layout the
+//     stack writer reads (+ their perspective counts): the learner's target side without the f32 detour.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,7 +37,7 @@ struct ReplayDev {        // device-resident state of a handle
     int64_t cursor;       // next ring position (SumTree.cursor)
     int64_t filled;       // SumTree.size
     int err;              // RP_ERR_* latch
-    int pad;
+    int werr;             // ERR_* latch of the stack writer (tq_replay_next_persp_write); read with `err`, which it follows
 };
 
 struct RingView {         // the wire block's sections without the priority section (the leaves carry it)
@@ -352,6 +354,41 @@ __global__ __launch_bounds__(256) void k_replay_gather(RingView r, const int64_t
         if (reward) reward[row] = ok ? r.reward[i] : 0.f;
         if (terminal) terminal[row] = ok ? r.terminal[i] : 0;
     }
+}
+
+// ------------------------------------------------------------------ next-state planes for the stack writer
+// nv / np of the records at idx[0..n) -> vp = u64[2][W][n], what k_pack_states makes of u8 grids and k_persp_stream
+// reads; one thread per (index, word), blockIdx.y = the word.  counts != NULL: the threads of word 0 also leave the
+// record's perspective count (Lat::persp_count of the whole planes: of the syndrome alone, whatever the terminal byte
+// says) and their block's level-1 sum for the scan.  An index outside [0, filled) reads nothing: its planes are zero,
+// its count 0, and RP_ERR_INDEX is latched.
+template <int D>
+__global__ __launch_bounds__(256) void k_replay_next_planes(RingView r, const int64_t* __restrict__ idx, int64_t n,
+                                                            ReplayDev* __restrict__ st, uint64_t* __restrict__ vp,
+                                                            int32_t* __restrict__ counts, int64_t* __restrict__ part256) {
+    using L = Lat<D>;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int k = blockIdx.y;
+    int cnt = 0;
+    if (e < n) {
+        const int64_t i = idx[e];
+        const bool ok = rp_index_ok(i, st);
+        vp[(int64_t)k * n + e] = ok ? r.nv[(int64_t)k * r.cap + i] : 0ull;
+        vp[((int64_t)L::W + k) * n + e] = ok ? r.np[(int64_t)k * r.cap + i] : 0ull;
+        if (k == 0) {
+            if (!ok) atomicOr(&st->err, RP_ERR_INDEX);
+            if (counts) {
+                typename L::B v = L::B::zero(), p = L::B::zero();
+                if (ok) {
+#pragma unroll
+                    for (int w = 0; w < L::W; ++w) { v.w[w] = r.nv[(int64_t)w * r.cap + i]; p.w[w] = r.np[(int64_t)w * r.cap + i]; }
+                }
+                cnt = L::persp_count(v, p);
+                counts[e] = cnt;
+            }
+        }
+    }
+    if (counts && k == 0) block_count_partial(cnt, part256);      // (uniform over the workgroup)
 }
 
 }  // namespace tq

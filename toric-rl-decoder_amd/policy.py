@@ -7,6 +7,7 @@ evaluation loop can run without the reference's Python.
 
   selectActionBatch    src/numba/util_actor.py:11-53
   predictMaxOptimized  src/util_learner.py:48-111
+  learnerTargets       src/Learner_mp.py:146-151 (targets straight from the device replay memory)
   evaluate             src/evaluation.py:10-124
 """
 import numpy as np
@@ -185,6 +186,37 @@ def predictMaxOptimized(model, batch_state, grid_shift, system_size, device, chu
     # the reference gives a terminal state one dummy perspective (:74-76), which counts for the padding
     largest = torch.clamp(counts.max(), min=1).to(torch.int32).reshape(1)
     return segment_max(q, offsets, largest)
+
+
+def td_target(q_table, offsets, reward, terminal, discount, lo=-100.0, hi=100.0):
+    """y = clamp(reward + (~terminal).float() * discount * m, lo, hi) with m = segment_max(q_table, offsets, largest)
+    -- the reference's zero padding included, the longest slice found on the device -- in one launch (tq_td_target),
+    bit-identical to that torch expression.  q_table f32 (P,3), offsets i64 (n+1,), reward f32 (n,), terminal bool
+    (n,) -> f32 (n,)."""
+    n = int(offsets.numel()) - 1
+    dev = q_table.device
+    q = to_device(q_table, torch.float32, dev)
+    r = to_device(reward, torch.float32, dev)
+    t = to_device(terminal, torch.bool, dev)
+    if r.numel() != n or t.numel() != n:
+        raise ValueError("reward / terminal must have one entry per state")
+    y = torch.empty(n, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(_lib.load().tq_td_target(_ptr(q), _ptr(offsets), n, _ptr(r), _ptr(t), float(discount), float(lo), float(hi),
+                                       _ptr(y), _stream()))
+    return y
+
+
+def learnerTargets(model, memory, indices, reward, terminal, discount=0.95, chunk=1 << 16):
+    """The learner's target side (Learner_mp.py:146-151: predictMaxOptimized on the batch's next_state, then
+    ``y = (reward + (~terminal) * discount * target).clamp(-100, 100)``) for a batch drawn from a device
+    PrioritizedReplayMemory: the next states' perspectives come straight from the ring's packed planes
+    (memory.next_perspectives), the target model runs on them in chunks, and tq_td_target does the reduction and the
+    arithmetic.  ``indices`` / ``reward`` / ``terminal``: as sample_batch returned them -> y f32 (n,)."""
+    model.eval()
+    persp, _, _, offsets = memory.next_perspectives(indices)
+    q = _forward_chunked(model, persp, chunk)
+    return td_target(q, offsets, reward, terminal, discount)
 
 
 def _greedy_episodes(envs, model, epsilon, num_of_steps, chunk):

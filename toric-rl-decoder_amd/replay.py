@@ -13,6 +13,7 @@ import torch
 
 from . import _lib, wire
 from ._lib import Handle, _ptr, _stream, check, to_device
+from .envset import _DTYPES
 from .transition import TransitionBlock
 
 MAX_BATCH = 4096
@@ -99,8 +100,9 @@ class PrioritizedReplayMemory(Handle):
         return int(n)
 
     def check(self):
-        """Reads and clears the device error latch (synchronises): ValueError for an index outside [0, filled) or a
-        draw that ended on an empty leaf, ToricEnvError for a sample of more records than are filled."""
+        """Reads and clears the device error latch (synchronises): ValueError for an index outside [0, filled), a draw
+        that ended on an empty leaf, or offsets next_perspectives' stack write refused; ToricEnvError for a sample of
+        more records than are filled, or a stack that did not fit its buffer."""
         self._call(self._L.tq_replay_check)
 
     def leaves(self):
@@ -113,10 +115,10 @@ class PrioritizedReplayMemory(Handle):
         self._call(self._L.tq_replay_tree, _ptr(out))
         return out
 
-    def _batch_outputs(self, n):
+    def _batch_outputs(self, n, next_state=True):
         d, dev = self.size, self.device
         return dict(state=torch.empty((n, 2, d, d), dtype=torch.float32, device=dev),
-                    next_state=torch.empty((n, 2, d, d), dtype=torch.float32, device=dev),
+                    next_state=torch.empty((n, 2, d, d), dtype=torch.float32, device=dev) if next_state else None,
                     actions=torch.empty(n, dtype=torch.int64, device=dev),
                     reward=torch.empty(n, dtype=torch.float32, device=dev),
                     terminal=torch.empty(n, dtype=torch.bool, device=dev),
@@ -131,6 +133,29 @@ class PrioritizedReplayMemory(Handle):
                    _ptr(out["actions"]), _ptr(out["reward"]), _ptr(out["terminal"]), _ptr(out["action"]))
         return out
 
+    def next_perspectives(self, indices, dtype=torch.float32):
+        """generatePerspectiveBatch(..., return_offsets=True) of the NEXT states of the records at ``indices`` (int64
+        device tensor or sequence, 1..4096 of them), read from the ring's packed planes as they are -- no f32
+        next_state, no u8 cast, no re-packing -> (stack (P,2,d,d) ``dtype``, positions (P,3) i32, counts i32 (n,),
+        offsets i64 (n+1,)).  An index outside [0, filled) (the -1 of an under-filled sample_batch) counts 0 and latches
+        an error for check().  One 8-byte read-back of P, as in generatePerspectiveBatch."""
+        idx = to_device(indices, torch.int64, self.device).reshape(-1)
+        n, d = int(idx.numel()), self.size
+        if not 1 <= n <= MAX_BATCH:
+            raise ValueError(f"need 1..{MAX_BATCH} indices")
+        if dtype not in _DTYPES:
+            raise ValueError(f"unsupported stack dtype {dtype}")
+        counts = torch.empty(n, dtype=torch.int32, device=self.device)
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        self._call(self._L.tq_replay_next_persp_count, _ptr(idx), n, _ptr(counts), _ptr(offsets))
+        P = int(offsets[-1].item())
+        out = torch.empty((P, 2, d, d), dtype=dtype, device=self.device)
+        pos = torch.empty((P, 3), dtype=torch.int32, device=self.device)
+        if P:
+            self._call(self._L.tq_replay_next_persp_write, _ptr(idx), n, _ptr(offsets), _ptr(out), _ptr(pos), P,
+                       _DTYPES[dtype])
+        return out, pos, counts, offsets
+
     # ---------------------------------------------------------------- sampling
     def _uniforms(self, u, n):
         u = to_device(u, torch.float64, self.device)
@@ -138,7 +163,7 @@ class PrioritizedReplayMemory(Handle):
             raise ValueError("need one uniform per draw")
         return u
 
-    def _sample(self, batch_size, beta, uniforms, records):
+    def _sample(self, batch_size, beta, uniforms, records, next_state=True):
         n = int(batch_size)
         if not 1 <= n <= MAX_BATCH:
             raise ValueError(f"batch_size must be in 1..{MAX_BATCH}")
@@ -146,7 +171,7 @@ class PrioritizedReplayMemory(Handle):
         idx = torch.empty(n, dtype=torch.int64, device=self.device)
         prio = torch.empty(n, dtype=torch.float64, device=self.device)
         w = torch.empty(n, dtype=torch.float64, device=self.device)
-        out = self._batch_outputs(n) if records else {}
+        out = self._batch_outputs(n, next_state) if records else {}
         g = lambda k: _ptr(out.get(k))
         self._call(self._L.tq_replay_sample, n, float(beta), _ptr(u), _ptr(idx), _ptr(prio), _ptr(w), g("state"),
                    g("next_state"), g("actions"), g("reward"), g("terminal"), g("action"))
@@ -169,11 +194,13 @@ class PrioritizedReplayMemory(Handle):
         records, _ = wire.to_records(dec, self.size)
         return records, w.cpu().numpy(), idx.cpu().numpy(), prio.cpu().numpy()
 
-    def sample_batch(self, batch_size, beta, uniforms=None):
+    def sample_batch(self, batch_size, beta, uniforms=None, next_state=True):
         """sample + dataToBatch (util_learner.py:7-46) without leaving the device -> (state f32 (B,2,d,d), actions i64
         (op - 1), reward f32, next_state f32 (B,2,d,d), terminal bool, weights f32, indices i64), all device tensors.
+        ``next_state=False``: the f32 next_state is neither allocated nor written and None stands in its place (a
+        learner that takes its targets from policy.learnerTargets reads the next states from the ring by index).
         No synchronisation: an under-filled memory latches an error that check() reports."""
-        idx, _, w, out = self._sample(batch_size, beta, uniforms, True)
+        idx, _, w, out = self._sample(batch_size, beta, uniforms, True, next_state)
         return out["state"], out["actions"], out["reward"], out["next_state"], out["terminal"], w.to(torch.float32), idx
 
     # ---------------------------------------------------------------- priorities
