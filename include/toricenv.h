@@ -380,6 +380,37 @@ int tq_replay_tree(tq_replay* r, double* out, void* stream);
 /* Reads and clears the handle's device error latch (synchronises `stream`). */
 int tq_replay_check(tq_replay* r, void* stream);
 
+/* ---- The Q-network NN_11's forward pass on the device (src/nn/torch/NN.py:10-45: eleven conv3x3 + ReLU with channels
+ * 2-128-128-120-111-104-103-90-80-73-71-64 and one linear layer to 3 outputs; src/nn/torch/util.py:21-26: the circular pad
+ * of 1 before the unpadded conv1; zero padding 1 in conv2..10, conv11 unpadded).  It reads the perspective stack
+ * tq_persp_write produces, in any of its four element types, and writes the (P,3) f32 Q-table that tq_select_action,
+ * tq_segment_max and tq_td_target consume.  Design: DESIGN.md 3.6.
+ * Numerics contract:
+ *  - conv and linear weights are rounded once to bf16 (round to nearest even) when they are loaded; all biases stay f32.
+ *  - a stack element is converted to bf16 (exact for the 0/1 the writer produces).
+ *  - each conv layer accumulates bf16 x bf16 products in f32 (MFMA), adds the f32 bias, applies ReLU in f32 and rounds to
+ *    bf16 (RNE) as the next layer's input; conv11's output is rounded the same way.
+ *  - the linear layer accumulates in f32, adds the f32 bias and stores f32: Q-values are never rounded to 16 bits.
+ *  - no atomics: the same call on the same inputs gives bit-identical output.
+ *  - channels are padded with zero weights and biases up to the MFMA granule (32), so a padded activation channel is 0.
+ * One handle, one stream: the calls of a handle share its packed weights and activation scratch; issue them on one
+ * stream, or separate them by a synchronisation.  create / destroy are set-up calls (allocate, synchronise, leave the
+ * caller's device unchanged); load and forward only enqueue kernels. */
+typedef struct tq_nn11 tq_nn11;
+/* NN_11(system_size = d, number_of_actions = 3) (NN.py:10-24) for passes of up to max_rows perspectives: allocates the
+ * packed weights and two activation images of max_rows * d*d * 128 bf16.  Checked before the device is touched: out NULL,
+ * d even or unsupported, max_rows <= 0 -> TQ_E_INVALID. */
+int tq_nn11_create(tq_nn11** out, int d, int64_t max_rows, int device);
+int tq_nn11_destroy(tq_nn11* h);
+/* model.load_state_dict (NN.py:10-24): weights[12] / biases[12] are HOST arrays of device pointers to f32 tensors in torch
+ * layout -- conv1..conv11 weight [cout][cin][3][3] and bias [cout], then linear1 weight [3][64*(d-2)^2] (features in
+ * (channel, y, x) order) and bias [3].  Packs on the device; cheap enough for a weight refresh at every flush. */
+int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* biases, void* stream);
+/* model(stack) (NN.py:26-45, util.py:21-26): stack[rows][2][d][d] of element type dtype (TQ_F32 / TQ_F16 / TQ_BF16 /
+ * TQ_U8, 16-byte aligned) -> q f32[rows][3].  Any rows >= 0: the call walks passes of max_rows itself.  TQ_E_INVALID
+ * before the first tq_nn11_load. */
+int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

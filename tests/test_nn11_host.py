@@ -1,0 +1,122 @@
+"""The NN_11 forward without a GPU: the host side of toric-rl-decoder_amd/csrc/nn11.hpp -- the pack routine, the index
+functions of the weight / activation / linear images and the tap -> source pixel map that the HIP kernels use -- built
+with g++ through tests/host_nn11_shim.cpp and driven by a scalar forward under the numerics contract of
+include/toricenv.h.  Test-only build: the product itself has no CPU path."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+import toric_rl_decoder_amd as T
+
+import nn11_cases as K
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def shim(tmp_path_factory):
+    out = tmp_path_factory.mktemp("nn11shim") / "libnn11shim.so"
+    subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared",
+                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "host_nn11_shim.cpp"), "-o", str(out)])
+    lib = C.CDLL(str(out))
+    lib.shim_nn11_forward.restype = C.c_int
+    lib.shim_nn11_forward.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64,
+                                      C.c_void_p]
+    return lib
+
+
+def shim_forward(shim, sd, d, per):
+    w = [np.ascontiguousarray(sd[n + ".weight"].numpy(), np.float32) for n in K.NAMES]
+    b = [np.ascontiguousarray(sd[n + ".bias"].numpy(), np.float32) for n in K.NAMES]
+    wp = (C.c_void_p * 12)(*[a.ctypes.data for a in w])
+    bp = (C.c_void_p * 12)(*[a.ctypes.data for a in b])
+    per = np.ascontiguousarray(per, np.uint8)
+    q = np.full((per.shape[0], 3), np.nan, np.float32)
+    assert shim.shim_nn11_forward(d, wp, bp, per.ctypes.data, per.shape[0], q.ctypes.data) == 0
+    return q
+
+
+@pytest.mark.parametrize("d", K.SIZES)
+def test_exact_integer_network_equals_torch_f32_bit_for_bit(shim, d):
+    """Every activation is a small integer (asserted on torch's own f32 result), so bf16 storage and any summation
+    order are exact: the shim's Q-table must be torch's.  Pins every tap, the three paddings, the odd channel counts
+    and their zero padding, and the linear layer's feature order."""
+    assert shim.shim_nn11_group(d) == max(1, 256 // (d * d))          # the G tests/test_gpu_nn11.py takes its row counts from
+    sd = K.integer_state_dict(d)
+    model = K.model_of(sd, d)
+    per, _ = K.stack_of(d, 64)
+    rows = per.shape[0]
+    q_torch = np.empty((rows, 3), np.float32)
+    seen, nonzero = set(), 0
+    for i in range(0, rows, 256):
+        outs, q = K.layer_outputs(model, torch.from_numpy(per[i:i + 256]).float())
+        for a in outs:
+            assert bool((a == a.round()).all()) and float(a.max()) < 256
+        q_torch[i:i + 256] = q.numpy()
+        last = outs[-1].flatten(1).to(torch.uint8).numpy()
+        seen.update(hash(r.tobytes()) for r in last)
+        nonzero += int(last.any(axis=1).sum())
+    if d >= 5:
+        assert len(seen) >= 0.99 * rows, (len(seen), rows)
+    assert nonzero > 0
+    got = shim_forward(shim, sd, d, per)
+    assert np.array_equal(got, q_torch), (d, int((got != q_torch).any(axis=1).sum()), rows)
+
+
+@pytest.mark.parametrize("d", (5, 7))
+def test_trained_weights_stay_within_twice_the_contracts_own_rounding_error(shim, d):
+    """rms error against torch's f32 forward <= 2 x that of the contract restated in torch ops (K.contract_forward): the
+    shim sums in another order than torch, which flips single bf16 roundings -- noise of the roundings' own size; a wrong
+    tap, bias or pad gives errors of the size of Q itself."""
+    sd = K.trained_state_dict(d)
+    model = K.model_of(sd, d)
+    per, _ = K.stack_of(d, 256)
+    x = torch.from_numpy(per).float()
+    with torch.no_grad():
+        q32 = torch.cat([model(x[i:i + 2048]) for i in range(0, x.shape[0], 2048)])
+    yard = torch.cat([K.contract_forward(model, x[i:i + 2048]) for i in range(0, x.shape[0], 2048)])
+    got = torch.from_numpy(shim_forward(shim, sd, d, per))
+    e_yard, e_got = K.rms(yard, q32), K.rms(got, q32)
+    print(f"d={d}: {x.shape[0]} perspectives, Q in [{float(q32.min()):.1f}, {float(q32.max()):.1f}], "
+          f"rms error vs f32: yardstick {e_yard:.4f}, shim {e_got:.4f}")
+    assert e_yard > 0
+    assert e_got <= 2 * e_yard
+
+
+def test_create_rejects_bad_arguments_before_the_device_is_touched():
+    L = T.load()
+    h = C.c_void_p(None)
+    for d, max_rows in ((4, 64), (8, 64), (23, 64), (1, 64), (7, 0), (7, -5)):
+        assert L.tq_nn11_create(C.byref(h), d, max_rows, 0) == -1, (d, max_rows)      # TQ_E_INVALID
+        assert not h.value
+    assert L.tq_nn11_create(None, 7, 64, 0) == -1
+    assert L.tq_nn11_forward(None, None, 0, 0, None, None) == -1
+    assert L.tq_nn11_load(None, None, None, None) == -1
+    assert L.tq_nn11_destroy(None) == 0
+
+
+def test_the_wrapper_is_public_and_skips_the_shape_padding():
+    assert T.NN11Forward.any_rows is True and "NN11Forward" in T.__all__
+    assert not hasattr(T.NN_11(5), "any_rows")
+    from toric_rl_decoder_amd.policy import _forward_chunked
+
+    class Rows:
+        def __init__(self, any_rows):
+            self.seen = []
+            if any_rows:
+                self.any_rows = True
+
+        def __call__(self, x):
+            self.seen.append(x.shape[0])
+            return torch.zeros((x.shape[0], 3))
+
+    x = torch.zeros((2500, 2, 3, 3))
+    new, old = Rows(True), Rows(False)
+    _forward_chunked(new, x, 2048)
+    _forward_chunked(old, x, 2048)
+    assert new.seen == [2048, 452] and old.seen == [2048, 1024]        # a torch module is padded as before

@@ -84,6 +84,10 @@ SYMBOLS = [
     ("tq_replay_tree_nodes", _i64, [_vp]),
     ("tq_replay_tree", _i, [_vp, _vp, _vp]),
     ("tq_replay_check", _i, [_vp, _vp]),
+    ("tq_nn11_create", _i, [C.POINTER(_vp), _i, _i64, _i]),
+    ("tq_nn11_destroy", _i, [_vp]),
+    ("tq_nn11_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("tq_nn11_forward", _i, [_vp, _vp, _i, _i64, _vp, _vp]),
 ]
 
 _lib = None

@@ -718,3 +718,4 @@ int tq_check(tq_env* h, void* stream_) {
 }  // extern "C"
 
 #include "abi_replay.hpp"
+#include "abi_nn11.hpp"

@@ -1,22 +1,26 @@
 """Policy-side glue around the env kernels (callers of the hot path).
 
-The Q-network itself is stock torch convolution work and out of scope; NN_11 is restated here
-(30 lines, same parameter names as the reference so its state_dicts load unchanged) only so that
-BASELINE configs[2] ("generatePerspective feeding NN_11 policy for selectAction") and the
-evaluation loop can run without the reference's Python.
+The Q-network NN_11 is restated here as a torch module (30 lines, same parameter names as the reference so
+its state_dicts load unchanged) so that BASELINE configs[2] ("generatePerspective feeding NN_11 policy for
+selectAction") and the evaluation loop can run without the reference's Python.  Its forward pass also exists as
+hand-written HIP (csrc/nn11.hpp behind tq_nn11_*): NN11Forward wraps a model's weights and is accepted wherever a
+``model`` is.
 
   selectActionBatch    src/numba/util_actor.py:11-53
   predictMaxOptimized  src/util_learner.py:48-111
   learnerTargets       src/Learner_mp.py:146-151 (targets straight from the device replay memory)
   evaluate             src/evaluation.py:10-124
+  NN11Forward          src/nn/torch/NN.py:10-45, src/nn/torch/util.py:21-26 (the forward as bf16 MFMA kernels)
 """
+import ctypes as C
+
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import _ptr, _stream, check, to_device
+from ._lib import Handle, _ptr, _stream, check, require_gpu, to_device
 from .envset import EnvSet, ToricEnv, generatePerspectiveBatch
 
 
@@ -42,6 +46,70 @@ class NN_11(nn.Module):
         return self.linear1(x.flatten(1))
 
 
+_STACK_DTYPES = {torch.float32: _lib.TQ_F32, torch.float16: _lib.TQ_F16, torch.bfloat16: _lib.TQ_BF16, torch.uint8: _lib.TQ_U8}
+
+
+class NN11Forward(Handle):
+    """NN_11's forward pass as HIP kernels (tq_nn11_*; numerics contract in include/toricenv.h): bf16 weights and
+    activations, f32 accumulation, f32 Q-values.  Callable like the model it was made from -- ``f(persp) -> (rows, 3)``
+    float32 tensor on the device, for a perspective stack (rows, 2, d, d) of float32, float16, bfloat16 or uint8 -- so
+    every function of this package that takes ``model`` takes it as well.  ``model_or_state_dict``: an NN_11 (or the
+    reference's) or its state_dict, with exactly NN_11's parameter names; ``load()`` refreshes the weights (packed on the
+    device, no allocation).  Any row count costs the same per row (``any_rows``): _forward_chunked does not pad for it.
+    One handle, one stream: calls share the handle's activation scratch, sized for ``max_rows`` rows per pass."""
+
+    any_rows = True
+    _destroy = "tq_nn11_destroy"
+
+    def __init__(self, model_or_state_dict, system_size, device, max_rows=1 << 16):
+        self.device = require_gpu(device)
+        self.system_size = int(system_size)
+        self._L = _lib.load()
+        self._h = C.c_void_p(None)
+        check(self._L.tq_nn11_create(C.byref(self._h), self.system_size, int(max_rows), self.device.index))
+        self.load(model_or_state_dict)
+
+    def load(self, model_or_state_dict):
+        sd = model_or_state_dict.state_dict() if hasattr(model_or_state_dict, "state_dict") else model_or_state_dict
+        names = [f"conv{i + 1}" for i in range(11)] + ["linear1"]
+        want = {f"{n}.{k}" for n in names for k in ("weight", "bias")}
+        if set(sd.keys()) != want:
+            raise ValueError(f"state_dict must have exactly NN_11's parameters; differs in {sorted(set(sd.keys()) ^ want)}")
+        ch, feats = NN_11.CHANNELS, 64 * (self.system_size - 2) ** 2
+        shapes = [(ch[i + 1], ch[i], 3, 3) for i in range(11)] + [(3, feats)]
+        w = [to_device(sd[n + ".weight"].detach(), torch.float32, self.device) for n in names]
+        b = [to_device(sd[n + ".bias"].detach(), torch.float32, self.device) for n in names]
+        for n, wt, bt, shape in zip(names, w, b, shapes):
+            if tuple(wt.shape) != shape or tuple(bt.shape) != shape[:1]:
+                raise ValueError(f"{n}: weight {tuple(wt.shape)} / bias {tuple(bt.shape)}, expected {shape} / {shape[:1]}")
+        wp = (C.c_void_p * 12)(*[t.data_ptr() for t in w])
+        bp = (C.c_void_p * 12)(*[t.data_ptr() for t in b])
+        self._call(self._L.tq_nn11_load, wp, bp)           # the pack kernel reads w / b on the current stream, where
+        return self                                        # any copies made above are freed in stream order
+
+    def __call__(self, persp):
+        if persp.dtype not in _STACK_DTYPES:
+            raise ValueError(f"stack dtype {persp.dtype} not one of float32 / float16 / bfloat16 / uint8")
+        d = self.system_size
+        if persp.dim() != 4 or tuple(persp.shape[1:]) != (2, d, d) or persp.device != self.device:
+            raise ValueError(f"expected a (rows, 2, {d}, {d}) stack on {self.device}, got {tuple(persp.shape)} on {persp.device}")
+        persp = persp.contiguous()
+        q = torch.empty((persp.shape[0], 3), dtype=torch.float32, device=self.device)
+        self._call(self._L.tq_nn11_forward, _ptr(persp), _STACK_DTYPES[persp.dtype], persp.shape[0], _ptr(q))
+        return q
+
+    forward = __call__
+
+    def eval(self):
+        return self
+
+    def train(self, mode=True):
+        return self
+
+    def to(self, *args, **kwargs):                         # evaluate() moves its model to the device: it is there already
+        return self
+
+
 def _forward_chunked(model, persp, chunk, pad_to=1024, backing=None, out=None):
     """model(persp) in chunks of `chunk` rows -> (rows, 3) float32.  The number of perspectives changes every step, and
     every new batch size is a new problem for MIOpen's solver search, so the last, ragged chunk is run at a row count
@@ -59,7 +127,7 @@ def _forward_chunked(model, persp, chunk, pad_to=1024, backing=None, out=None):
         for i in range(0, n, chunk):
             x = persp[i:i + chunk]
             r = x.shape[0]
-            if r < chunk and pad_to > 1 and r % pad_to:
+            if r < chunk and pad_to > 1 and r % pad_to and not getattr(model, "any_rows", False):
                 rows = min(chunk, (r + pad_to - 1) // pad_to * pad_to)
                 if backing is not None and backing.data_ptr() == persp.data_ptr() and backing.shape[0] >= i + rows:
                     xp = backing[i:i + rows]
