@@ -41,6 +41,17 @@ __global__ void k_diff(const uint32_t* a, const uint32_t* b, int64_t n, unsigned
     if (c) atomicAdd(bad, c);
 }
 
+// all cut points of a lattice range as a table, by the stream kernel's own search (tq::find_cut): checked below against
+// the scan's by-product and the host's search
+__global__ __launch_bounds__(256) void k_split(const int64_t* __restrict__ offsets, int64_t e_begin, int64_t e_end,
+                                               int32_t* __restrict__ split, int LG) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (k > (1 << LG)) return;
+    const int64_t e = tq::find_cut(offsets, e_begin, e_end, k, LG, lane);
+    if (lane == 0) split[k] = (int32_t)e;
+}
+
 // One virtual range backed by physical chunks of `chunk` bytes mapped in a SHUFFLED order (HIP virtual memory API):
 // consecutive chunks of the buffer lie in unrelated places of the HBM.
 static float* alloc_shuffled(size_t bytes, size_t chunk, unsigned seed) {
@@ -143,7 +154,7 @@ int run(int64_t N, double q) {
     hipLaunchKernelGGL(k_counts<D>, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, 0, vp, counts, N, part);
     hipLaunchKernelGGL(tq::k_scan_final, dim3((unsigned)((N + tq::SCAN_CHUNK - 1) / tq::SCAN_CHUNK)), dim3(256), 0, 0, counts,
                        (const int64_t*)part, off, (int32_t*)nullptr, N, split, 8);
-    hipLaunchKernelGGL(tq::k_split, dim3((256 + 1 + 3) / 4), dim3(256), 0, 0, (const int64_t*)off, (int64_t)0, N, split2, 8);
+    hipLaunchKernelGGL(k_split, dim3((256 + 1 + 3) / 4), dim3(256), 0, 0, (const int64_t*)off, (int64_t)0, N, split2, 8);
     CK(hipDeviceSynchronize());
     int32_t hs[257], hs2[257];
     CK(hipMemcpy(hs, split, 4 * 257, hipMemcpyDeviceToHost)); CK(hipMemcpy(hs2, split2, 4 * 257, hipMemcpyDeviceToHost));
@@ -155,7 +166,7 @@ int run(int64_t N, double q) {
         for (auto& r : ranges) {
             if (r[1] > N) continue;
             CK(hipMemset(split2, 0xff, 4 * 264));
-            hipLaunchKernelGGL(tq::k_split, dim3((256 + 1 + 3) / 4), dim3(256), 0, 0, (const int64_t*)off, r[0], r[1], split2, 8);
+            hipLaunchKernelGGL(k_split, dim3((256 + 1 + 3) / 4), dim3(256), 0, 0, (const int64_t*)off, r[0], r[1], split2, 8);
             CK(hipMemcpy(hs2, split2, 4 * 257, hipMemcpyDeviceToHost));
             int nbad = 0, first_bad = -1;
             for (int k = 0; k <= 256; ++k) {
@@ -184,7 +195,7 @@ int run(int64_t N, double q) {
             constexpr int WV = 16;
             unsigned long long* st; CK(hipMalloc(&st, 8 * 256 * WV * 4)); CK(hipMemset(st, 0, 8 * 256 * WV * 4));
             hipLaunchKernelGGL((tq::k_persp_write<D, float, 64>), dim3((unsigned)(r[1] - r[0])), dim3(64), 0, 0, vp, N, off, a, pa, Pr, err, r[0], r[1]);
-            hipLaunchKernelGGL(tq::k_split, dim3((256 + 1 + 3) / 4), dim3(256), 0, 0, (const int64_t*)off, r[0], r[1], split2, 8);
+            hipLaunchKernelGGL(k_split, dim3((256 + 1 + 3) / 4), dim3(256), 0, 0, (const int64_t*)off, r[0], r[1], split2, 8);
             hipLaunchKernelGGL((tq::k_persp_stream<D, float, 4, 11, 8, 14, 12, true>), dim3(256), dim3(1024), 0, 0, vp, N, off, b, pb, Pr, err, r[0], r[1], (const int32_t*)split2, 8, 0, (unsigned int*)nullptr, st);
             hipLaunchKernelGGL(k_diff, dim3(256), dim3(256), 0, 0, (const uint32_t*)a, (const uint32_t*)b, Pr * NQ, badr);
             hipLaunchKernelGGL(k_diff, dim3(256), dim3(256), 0, 0, (const uint32_t*)pa, (const uint32_t*)pb, Pr * 3, badr);

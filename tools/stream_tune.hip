@@ -82,11 +82,11 @@ struct Ctx {
 
 // KIND: 2 = the library's kernel (fine parts from the scan's table, c.bias); 0 = the experiment of tools/stream_write_runs.hpp,
 // runs behind the main runs taken by ticket (schedule SCHED); 1 = the same, one run per workgroup
-template <int D, typename OutT, int NS, int NPW, int NP, int CPW, int RB, int RP, int QS, int KIND, int SCHED, bool STATS>
+template <int D, typename OutT, int NS, int NPW, int NP, int CPW, int RB, int RP, int KIND, int SCHED, bool STATS>
 void launch_kind(Ctx& c, int grid, const int32_t* sp, unsigned long long* st) {
     constexpr int WV = NS + NPW + NP;
     if constexpr (KIND == 2) {
-        hipLaunchKernelGGL((tq::k_persp_stream<D, OutT, NS, NP, CPW, RB, RP, STATS, NPW, QS>), dim3(grid), dim3(64 * WV), 0, 0, c.vp, c.N, c.off,
+        hipLaunchKernelGGL((tq::k_persp_stream<D, OutT, NS, NP, CPW, RB, RP, STATS, NPW>), dim3(grid), dim3(64 * WV), 0, 0, c.vp, c.N, c.off,
                            (OutT*)c.out, c.pos, c.P, c.err, (int64_t)0, c.N, sp ? c.split_fine : nullptr, grid == 256 ? 13 : 14, c.bias,
                            c.ticket + 8 + tq::STREAM_SLOT_WORDS * (c.launches % 8), st);
         ++c.launches;
@@ -103,11 +103,11 @@ void launch_kind(Ctx& c, int grid, const int32_t* sp, unsigned long long* st) {
 
 // GRID: workgroups (a power of two; 256 = one per CU with the scan's cut points, 512 = two per CU -- needs <= 80 KB of LDS --
 // which find their cut points themselves)
-template <int D, typename OutT, int NS, int NPW, int NP, int CPW, int RB, int RP, int GRID = 256, int QS = 1, int KIND = 0, int SCHED = 0>
+template <int D, typename OutT, int NS, int NPW, int NP, int CPW, int RB, int RP, int GRID = 256, int KIND = 0, int SCHED = 0>
 void one(Ctx& c, bool stats, bool is_ref) {
     constexpr int WV = NS + NPW + NP;
     const int32_t* sp = GRID == 256 ? c.split : nullptr;
-    auto k = [&] { launch_kind<D, OutT, NS, NPW, NP, CPW, RB, RP, QS, KIND, SCHED, false>(c, GRID, sp, nullptr); };
+    auto k = [&] { launch_kind<D, OutT, NS, NPW, NP, CPW, RB, RP, KIND, SCHED, false>(c, GRID, sp, nullptr); };
     CK(hipMemset(c.out, 0x77, c.out_bytes)); CK(hipMemset(c.pos, 0x77, (size_t)c.P * 12));
     k(); CK(hipDeviceSynchronize());
     unsigned long long nb = 0;
@@ -122,8 +122,8 @@ void one(Ctx& c, bool stats, bool is_ref) {
     int e; CK(hipMemcpy(&e, c.err, 4, hipMemcpyDeviceToHost));
     float a = 0, mn = 1e9;
     for (int r = 0; r < 9; ++r) { float x = c.t->run(k); if (r) { a += x; mn = std::min(mn, x); } }
-    printf("  %s grid %d NS=%d NPW=%d NP=%2d CPW=%2d QS=%d %s %d  %7.1f us  %6.0f GB/s (best %6.0f)   %s, latch %d\n",
-           KIND == 0 ? "runs by ticket  " : (KIND == 1 ? "runs, one per wg" : "library kernel  "), GRID, NS, NPW, NP, CPW, QS, KIND == 2 ? "bias" : "sched", KIND == 2 ? c.bias : SCHED, 1e3 * a / 8,
+    printf("  %s grid %d NS=%d NPW=%d NP=%2d CPW=%2d %s %d  %7.1f us  %6.0f GB/s (best %6.0f)   %s, latch %d\n",
+           KIND == 0 ? "runs by ticket  " : (KIND == 1 ? "runs, one per wg" : "library kernel  "), GRID, NS, NPW, NP, CPW, KIND == 2 ? "bias" : "sched", KIND == 2 ? c.bias : SCHED, 1e3 * a / 8,
            c.bytes / (a / 8) / 1e6, c.bytes / mn / 1e6, is_ref ? "reference of this sweep" : (nb ? "DIFFERS" : "same bytes"), e);
     if (nb) printf("      %llu differing dwords\n", nb);
     if (!stats || GRID != 256) return;
@@ -132,7 +132,7 @@ void one(Ctx& c, bool stats, bool is_ref) {
     CK(hipMemset(st, 0, sizeof(unsigned long long) * 256 * WV * 4));
     for (int r = 0; r < 4; ++r) {                            // warm code; the last launch is the one read
         CK(hipMemset(st, 0, sizeof(unsigned long long) * 256 * WV * 4));
-        launch_kind<D, OutT, NS, NPW, NP, CPW, RB, RP, QS, KIND, SCHED, true>(c, 256, c.split, st);
+        launch_kind<D, OutT, NS, NPW, NP, CPW, RB, RP, KIND, SCHED, true>(c, 256, c.split, st);
         CK(hipDeviceSynchronize());
     }
     std::vector<unsigned long long> h((size_t)256 * WV * 4);
@@ -310,7 +310,7 @@ int run(int64_t N, double q, const char* tname) {
         for (int b = 0; b < 8; ++b) {
             printf(" buffer %d\n", b); c.out = bufs[b];
             const int biases[] = {0, 2, 3, 4, 5, 6, 0};
-            for (int i = 0; i < 7; ++i) { c.bias = biases[i]; one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 2, 0>(c, st && (i == 0 || i == 2 || i == 3), i == 0); }
+            for (int i = 0; i < 7; ++i) { c.bias = biases[i]; one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 2, 0>(c, st && (i == 0 || i == 2 || i == 3), i == 0); }
             c.bias = 0;
         }
         return 0;
@@ -320,12 +320,12 @@ int run(int64_t N, double q, const char* tname) {
         const bool st = getenv("TUNE_STATS") != nullptr;
         for (int b = 0; b < 8; ++b) {
             printf(" buffer %d\n", b); c.out = bufs[b];
-            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 2, 0>(c, st, true);
-            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 1, 0>(c, false, false);
-            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 0, 0>(c, st, false);
-            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 0, 1>(c, false, false);
-            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 0, 4>(c, st, false);
-            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 2, 0>(c, false, false);
+            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 2, 0>(c, st, true);
+            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 0>(c, false, false);
+            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 0, 0>(c, st, false);
+            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 0, 1>(c, false, false);
+            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 0, 4>(c, st, false);
+            one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 2, 0>(c, false, false);
         }
         return 0;
     }
@@ -338,48 +338,41 @@ int run(int64_t N, double q, const char* tname) {
     }
     if (getenv("TUNE_SPREAD")) {                              // the product configuration on EVERY candidate buffer, with the workgroups' end times
         constexpr int NPW0 = (ES < 4 && D >= 5) ? 2 : 1, NSP = D == 5 && ES == 2 ? 3 : NS0, NPP = D >= 17 ? 3 : (D >= 13 ? 8 - NPW0 : 16 - NSP - NPW0);
-        for (int b = 0; b < 8; ++b) { printf(" buffer %d\n", b); c.out = bufs[b]; one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 1, 2, 0>(c, true, b == 0); }
+        for (int b = 0; b < 8; ++b) { printf(" buffer %d\n", b); c.out = bufs[b]; one<D, OutT, NSP, NPW0, NPP, 8, 14, 12, 256, 2, 0>(c, true, b == 0); }
         return 0;
     }
-#define CFG(NS, NPW, NP, CPW, STATS, REF) one<D, OutT, NS, NPW, NP, CPW, 14, 12, 256, 1, 0, 0>(c, STATS, REF);
-#define CFQ(NS, NPW, NP, QS, STATS, REF) one<D, OutT, NS, NPW, NP, 8, 14, 12, 256, QS, 2, 0>(c, STATS, REF);
+    // (KIND: see launch_kind.  A sweep of the library's kernel ends with its first configuration once more, without the
+    // statistics: the drift of the box over the sweep)
+#define CFG(NS, NPW, NP, CPW, KIND, STATS, REF) one<D, OutT, NS, NPW, NP, CPW, 14, 12, 256, KIND, 0>(c, STATS, REF);
     if constexpr (D == 3) {
-        CFQ(2, 1, 13, 1, true, true)
-        CFQ(2, 1, 13, 8, true, false)
-        CFQ(2, 1, 13, 4, false, false)
-        CFQ(3, 1, 12, 8, false, false)
-        CFQ(4, 1, 11, 8, false, false)
-        CFQ(2, 2, 12, 8, false, false)
-        CFQ(2, 1, 13, 1, false, false)
+        CFG(2, 1, 13, 8, 2, true, true)
+        CFG(3, 1, 12, 8, 2, false, false)
+        CFG(4, 1, 11, 8, 2, false, false)
+        CFG(2, 2, 12, 8, 2, false, false)
+        CFG(2, 1, 13, 8, 2, false, false)
     } else if constexpr (D == 5) {
-        CFQ(2, 1, 13, 1, true, true)
-        CFQ(2, 1, 13, 4, true, false)
-        CFQ(2, 2, 12, 1, false, false)
-        CFQ(2, 2, 12, 4, true, false)
-        CFQ(3, 2, 11, 1, false, false)
-        CFQ(3, 2, 11, 4, false, false)
-        CFQ(4, 2, 10, 4, false, false)
-        CFQ(4, 1, 11, 4, false, false)
-        CFQ(2, 1, 13, 1, false, false)
+        CFG(2, 1, 13, 8, 2, true, true)
+        CFG(2, 2, 12, 8, 2, true, false)
+        CFG(3, 2, 11, 8, 2, false, false)
+        CFG(4, 2, 10, 8, 2, false, false)
+        CFG(4, 1, 11, 8, 2, false, false)
+        CFG(2, 1, 13, 8, 2, false, false)
     } else if constexpr (D >= 13) {
-        CFG(4, 1, 7, 8, true, true)
-        CFG(4, 1, 3, 8, true, false)
-        CFG(4, 2, 6, 8, ES < 4, false)
-        CFG(4, 1, 7, 8, false, false)
+        CFG(4, 1, 7, 8, 0, true, true)
+        CFG(4, 1, 3, 8, 0, true, false)
+        CFG(4, 2, 6, 8, 0, ES < 4, false)
+        CFG(4, 1, 7, 8, 0, false, false)
     } else if constexpr (D == 7) {
-        CFQ(4, 1, 11, 1, true, true)
-        CFQ(4, 1, 11, 3, true, false)
-        CFQ(4, 2, 10, 1, true, false)
-        CFQ(4, 2, 10, 3, true, false)
-        CFQ(4, 2, 10, 4, false, false)
-        CFQ(3, 2, 11, 3, false, false)
-        CFQ(4, 1, 7, 3, false, false)
-        CFQ(4, 1, 11, 1, false, false)
+        CFG(4, 1, 11, 8, 2, true, true)
+        CFG(4, 2, 10, 8, 2, true, false)
+        CFG(3, 2, 11, 8, 2, false, false)
+        CFG(4, 1, 7, 8, 2, false, false)
+        CFG(4, 1, 11, 8, 2, false, false)
     } else {
-        CFG(4, 1, 11, 8, true, true)
-        CFG(4, 2, 10, 8, true, false)
-        CFG(4, 3, 9, 8, false, false)
-        CFG(4, 1, 11, 8, false, false)
+        CFG(4, 1, 11, 8, 0, true, true)
+        CFG(4, 2, 10, 8, 0, true, false)
+        CFG(4, 3, 9, 8, 0, false, false)
+        CFG(4, 1, 11, 8, 0, false, false)
     }
     return 0;
 }

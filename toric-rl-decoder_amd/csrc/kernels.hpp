@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "env_step.hpp"
+#include "stream_range.hpp"
 #include "td_target.hpp"
 
 namespace tq {
@@ -453,7 +454,7 @@ __global__ __launch_bounds__(256) void k_scan_partials(const int32_t* __restrict
 }
 
 // `split` (may be NULL): cut points of the batch into G = 1 << LG parts of equal perspective count for the
-// stack write (stream_write.hpp): split[k] = first lattice e with offsets[e] >= (P * k) >> LG, k = 0..G.
+// stack write (stream_write.hpp): split[k] = first lattice e with offsets[e] >= cut_target(P, k, LG), k = 0..G.
 // A by-product of the scan: every thread knows the offsets around its eight lattices, the workgroup sums all
 // level-1 partials for P, and the thread whose interval holds a cut point writes it.  Behind the G + 1 cut points the
 // table carries a header of SPLIT_HEADER words -- P (low, high) and N -- by which the stack write tells that a table
@@ -527,7 +528,7 @@ __global__ __launch_bounds__(256) void k_scan_final(const int32_t* __restrict__ 
             if (blockIdx.x == 0) for (int k = tid; k <= G; k += 256) split[k] = 0;
         } else {
             // kfloor(x) = the largest k with T_k = (total * k) >> LG <= x: float estimate, exact fix-up
-            auto T = [&](int64_t k) { return (int64_t)(((uint64_t)total * (uint64_t)k) >> LG); };
+            auto T = [&](int64_t k) { return cut_target(total, k, LG); };
             auto kfloor = [&](int64_t x) {
                 int64_t k = (int64_t)((double)(x + 1) * (double)G / (double)total);
                 k = k < 0 ? 0 : (k > G ? G : k);
