@@ -21,5 +21,3 @@ extern "C" void shim_slot_fine_parts(int large, int idx, int rr, int bias, int32
     tq::slot_fine_parts(large, idx, rr, bias, lo, hi);
     lo_hi[0] = lo; lo_hi[1] = hi;
 }
-
-extern "C" int64_t shim_cut_target(int64_t total, int64_t k, int lg) { return tq::cut_target(total, k, lg); }

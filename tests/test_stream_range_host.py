@@ -28,8 +28,6 @@ def shim(tmp_path_factory):
     lib.shim_stream_range.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.shim_slot_fine_parts.restype = None
     lib.shim_slot_fine_parts.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    lib.shim_cut_target.restype = C.c_int64
-    lib.shim_cut_target.argtypes = [C.c_int64, C.c_int64, C.c_int]
     return lib
 
 
@@ -122,12 +120,3 @@ def test_slots_fine_parts_tile_the_table(shim, rr):
         got.sort()
         assert got[0][0] == 0 and got[-1][1] == WGS * rr, (rr, bias)
         assert all(a[1] == b[0] for a, b in zip(got, got[1:])), (rr, bias, got)
-
-
-def test_cut_target_is_the_floor_of_the_kth_share(shim):
-    rng = np.random.default_rng(5)
-    totals = [0, 1, 2, 255, 256, 257, 100003, 2**31 - 1, 2**31, 2**40 + 12345, 2**50 - 1] + [int(x) for x in rng.integers(0, 2**50, 20)]
-    for lg in (0, 1, 8, 13):
-        for total in totals:
-            for k in {0, 1, 2, (1 << lg) // 2, (1 << lg) - 1, 1 << lg} | {int(x) for x in rng.integers(0, (1 << lg) + 1, 8)}:
-                assert shim.shim_cut_target(total, k, lg) == (total * k) >> lg, (total, k, lg)

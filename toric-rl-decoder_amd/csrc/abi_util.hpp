@@ -70,7 +70,7 @@ __forceinline__ int launch_signal(void (*kernel)(P...), dim3 grid, dim3 block, h
 
 // the thread-per-item kernels: blocks of BLOCK_1D threads over n items
 constexpr int BLOCK_1D = 256;
-static_assert(BLOCK_1D == tq::PART_BLOCK, "block_count_partial (kernels.hpp) sums the counts of exactly one such block");
+static_assert(BLOCK_1D == tq::PART_BLOCK, "block_count_partial (scan.hpp) sums the counts of exactly one such block");
 inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + BLOCK_1D - 1) / BLOCK_1D)); }
 template <typename... P, typename... A>
 __forceinline__ int launch_1d(void (*kernel)(P...), int64_t n, hipStream_t stream, A&&... args) {

@@ -6,7 +6,7 @@
 // Tree: L levels (root = level 0), heap order, node n has children 2n+1 and 2n+2, leaf i is node 2^(L-1)-1+i and holds
 // record i.  Between calls every internal node is fl(left + right): no kernel adds into the tree with atomics, so the
 // tree is a function of its leaves.
-//   * ingest: flags (action word != 0) -> the project's two-level scan (kernels.hpp) -> k_replay_ingest copies the
+//   * ingest: flags (action word != 0) -> the project's two-level scan (scan.hpp) -> k_replay_ingest copies the
 //     non-empty slots in slot order to ring positions (cursor + k) % capacity and writes their leaves;
 //   * range rebuild: k_replay_chunks reduces 2048-leaf subtrees in LDS (one workgroup each, every internal node of the
 //     subtree written) and k_replay_top, one workgroup, the levels above them;

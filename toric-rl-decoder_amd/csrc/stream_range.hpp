@@ -1,15 +1,12 @@
 // Which bytes a workgroup of the stack write (stream_write.hpp) owns: plain integer arithmetic for host and device, like
 // the lattice algebra and the TD target -- the kernel and tests/test_stream_range_host.py (g++) call the same functions.
 #pragma once
-#include "lattice.hpp"
+#include "cut_points.hpp"
 
 namespace tq {
 
-// The stack is cut into 1 << LG fine parts of equal perspective count: part k begins at the first lattice whose offset
-// reaches this many perspectives (find_cut searches for it, k_scan_final writes all of them as a table).
-TQ_HD int64_t cut_target(int64_t total, int64_t k, int LG) { return (int64_t)(((uint64_t)total * (uint64_t)k) >> LG); }
-
-// Fine parts [f_lo, f_hi) of a slot.  Every pair of shares (2 RR fine parts) is cut into a LARGE slot of RR + bias parts
+// Fine parts [f_lo, f_hi) of a slot (the stack is cut into 1 << LG fine parts of equal perspective count at the cut points
+// of cut_points.hpp).  Every pair of shares (2 RR fine parts) is cut into a LARGE slot of RR + bias parts
 // and a SMALL one of RR - bias behind it; `idx` counts the pairs.
 TQ_HD void slot_fine_parts(int large, int idx, int RR, int bias, int& f_lo, int& f_hi) {
     f_lo = idx * 2 * RR + (large ? 0 : RR + bias);

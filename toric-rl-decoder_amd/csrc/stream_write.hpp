@@ -19,7 +19,7 @@
 // Output lines: the stack is cut into 128-byte lines and a workgroup stores the lines whose FIRST element lies
 // in its range, whole.  The trailing elements of its last line belong to the first lattice(s) of the next
 // range: its producers simply go on for the few perspectives that line needs (`need_extra`).  That arithmetic, the
-// slot -> fine parts mapping and the cut target are stream_range.hpp: host + device, tested without a GPU.
+// slot -> fine parts mapping is stream_range.hpp, the cut points are cut_points.hpp: host + device, tested without a GPU.
 //
 // The kernel, in the order of this file: stream_setup (workgroup-uniform: slot, cut points, capacity, range), one function
 // per role -- storer_wave, positions_wave, producer_wave -- and the entry k_persp_stream, which runs the set-up and
@@ -282,16 +282,11 @@ __device__ __forceinline__ bool stream_setup(StreamCtx<typename K::Out>& c, type
     }
     int f_lo, f_hi;
     slot_fine_parts(slot_s[0], slot_s[1], RR, bias, f_lo, f_hi);
-    // A table is followed only if it is the table of THESE offsets over THIS lattice range: its header (k_scan_final) holds
+    // A table is followed only if it is the table of THESE offsets over THIS lattice range: its header (cut_points.hpp) holds
     // the stack's perspective count and the last lattice, and a scan covers [0, N].  The handle matches tables to offsets
     // POINTERS; a caller who refilled a scanned array hands in a table of another stack -- all zero, say, which would leave
     // the stack unwritten with nothing latched.  Such a table is not followed: the workgroups find their cut points themselves.
-    bool by_tab = false;
-    if (split) {
-        const int G = 1 << lg;
-        const int64_t t_all = (int64_t)(((uint64_t)(uint32_t)split[G + 2] << 32) | (uint32_t)split[G + 1]);
-        by_tab = t_all == p_tab && e_begin == 0 && (int64_t)split[G + 3] == e_end;
-    }
+    const bool by_tab = split && cut_header_matches(split, lg, p_tab, e_begin, e_end);
     int64_t e_lo, e_hi;
     if (by_tab) {
         e_lo = split[f_lo]; e_hi = split[f_hi];

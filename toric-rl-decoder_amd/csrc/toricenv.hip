@@ -25,7 +25,6 @@ struct DeviceCtx {
 };
 constexpr int SPLIT_MAX = 256;       // persistent workgroups of the stack write: one per CU of an MI355X
 constexpr int SPLIT_LG = 13;         // the scan's table cuts the stack into 1 << SPLIT_LG fine parts: 32 per workgroup
-constexpr int SPLIT_ENTRIES = (1 << SPLIT_LG) + 1;   // + SPLIT_HEADER words behind them (k_scan_final): allocated as SPLIT_ENTRIES + 3
 constexpr int N_SLOT_SETS = 8;       // sets of slot counters of the stack write, used in turn
 // Fine parts (of 32) that the workgroup of an odd XCD hands to its even neighbour (stream_write.hpp: the odd XCDs of an
 // MI355X store ~20 % slower; sweep in profiles/r04_xcd_bias_sweep.txt).  tq_set_xcd_bias / TORICENV_XCD_BIAS = 0..16.
@@ -239,8 +238,7 @@ int tq_create(tq_env** out, int n_envs, int d, int device, uint64_t seed, int64_
     m.zeroed(&h->err, 4);
     m.zeroed(&h->mark, N * 4);
     m.zeroed(&h->tblock, (size_t)tq::block_bytes(h->w, n_envs));
-    m.zeroed(&h->split[0], (SPLIT_ENTRIES + 3) * sizeof(int32_t));
-    m.zeroed(&h->split[1], (SPLIT_ENTRIES + 3) * sizeof(int32_t));
+    for (int32_t*& t : h->split) m.zeroed(&t, (size_t)tq::cut_table_words(SPLIT_LG) * sizeof(int32_t));
     m.zeroed(&h->slots, N_SLOT_SETS * tq::STREAM_SLOT_WORDS * sizeof(unsigned int));
     if (const hipError_t e = m.err; e != hipSuccess) { tq_destroy(h); return fail(TQ_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
     if (int rc = get_lut(device, d, nullptr, &h->lut)) { tq_destroy(h); return rc; }
