@@ -35,7 +35,7 @@ def sample_tree(tree, capacity, uniforms, beta):
     """PrioritizedReplayMemory.sample on a copy of ``tree`` with the draws ``uniforms`` -> (indices, weights,
     priorities, tree after the draws, before the revert).  Weights that are all 0 come back as zeros (the reference
     raises ZeroDivisionError)."""
-    t = [float(x) for x in tree]
+    t = np.asarray(tree, np.float64).tolist()
     L = levels(capacity)
     base = (1 << (L - 1)) - 1
     idx, pri, w = [], [], []
@@ -125,6 +125,29 @@ def uniforms(seed, call, n):
     k = np.arange(n, dtype=np.uint64)
     w0, w1, _, _ = philox4x32(call & 0xFFFFFFFF, call >> 32, 0, (5 << 24) | k, seed & 0xFFFFFFFF, seed >> 32)
     return ((w0 >> 5).astype(np.float64) * 67108864.0 + (w1 >> 6).astype(np.float64)) * (1.0 / 9007199254740992.0)
+
+
+def segment_draws(capacity):
+    """Inputs that send the sampler's later picks below the staged levels into subtrees that earlier picks already
+    corrected -> (leaf values in [0.01, 10) with a tenth of them 0, 64 uniforms).  The uniforms come in equal pairs; the
+    first pair is 0.0 (leaf 0 twice, the second time at priority 0 and weight 0), the last the largest double below 1."""
+    rng = np.random.default_rng(capacity)
+    leaves = rng.uniform(0.01, 10, capacity)
+    leaves[rng.random(capacity) < 0.1] = 0.0
+    u = np.repeat(rng.uniform(0, 1, 32), 2)
+    u[0] = u[1] = 0.0
+    u[62] = u[63] = 1 - 2.0 ** -53
+    return leaves, u
+
+
+def picks_sharing_the_bottom_segment(indices, capacity, staged=13, seg=6):
+    """How many of the picks lie under the same bottom segment of the sampler as an earlier pick: the levels below the
+    top ``staged`` ones are walked in subtrees of depth ``seg`` and a last one of what remains (0 without segments)."""
+    below = levels(capacity) - staged
+    if below <= 0:
+        return 0
+    roots = [int(i) >> ((below - 1) % seg + 1) for i in indices]
+    return sum(r in roots[:k] for k, r in enumerate(roots))
 
 
 def close(a, b, rel=1e-12):

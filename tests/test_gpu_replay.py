@@ -207,6 +207,30 @@ def test_philox_draws_match_the_oracle_on_the_devices_tree(faithful):
     mem.close()
 
 
+@pytest.mark.parametrize("cap,faithful", [(5000, True), (40_000, True), (40_000, False), (300_000, True)])
+def test_draws_below_the_staged_levels_match_the_oracle(cap, faithful):
+    """The smallest capacities whose levels below the staged ones are a lone short segment (1 level), a mid-depth one (4)
+    and a full one followed by a short one (6 + 1), with draws that come back to segments earlier picks corrected."""
+    d, alpha, beta = 3, 0.6, 0.4
+    prios, u = RO.segment_draws(cap)
+    mem = T.PrioritizedReplayMemory(cap, alpha, d=d, device=DEV, seed=7, faithful=faithful)
+    mem.save_block(synthetic_block(d, prios, seed=cap))
+    assert mem.filled_size() == cap
+    tree0 = mem.tree().cpu().numpy()
+    _, w, idx, p = mem.sample(u.size, beta, uniforms=u)
+    oi, ow, op, _ = RO.sample_tree(tree0, cap, u, beta)
+    shared = RO.picks_sharing_the_bottom_segment(oi, cap)
+    assert shared >= 5, f"only {shared} of the oracle's picks share a bottom segment with an earlier one"
+    assert np.array_equal(idx, oi), "indices"
+    assert np.array_equal(p, op), "priorities"
+    assert np.all(ulps(w, ow) <= 2.0), "weights"
+    if not faithful:
+        assert np.array_equal(mem.tree().cpu().numpy(), tree0), "faithful=False: a sample must leave the tree untouched"
+    assert_canonical(mem)
+    mem.check()
+    mem.close()
+
+
 def test_priority_update_last_occurrence_wins_and_tree_stays_canonical():
     d, cap, alpha = 5, 50_000, 0.7
     mem = T.PrioritizedReplayMemory(cap, alpha, d=d, device=DEV)

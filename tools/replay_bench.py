@@ -5,6 +5,7 @@ Device part (default): HIP-event times of the device replay memory after a warm-
   * ingest: save_block of one 65 536 x 8-slot block (every slot a transition) at d=7 and d=9, capacity 10^6;
   * sample_batch latency at capacity 10^6 (filled) for B = 16, 256, 1024 (sample + records + faithful revert);
   * update_priorities latency for the same B.
+  --lib SO: with another build of libtoricenv.so (a parent commit's, for an A/B in alternating processes).
 Targets leg (--targets): the learner's target side at capacity 10^6 (actor-written records), B = 32, 256, 1024 and
 d = 7, 9, old path against new, each the median of 200 calls after 20 warm-ups, timed alternately in seven pairs --
   * old: sample_batch's f32 next_state -> generatePerspectiveBatch -> segment_max + the torch target expression;
@@ -194,7 +195,11 @@ def main():
     ap.add_argument("--host", metavar="REFERENCE_DIR", help="time the reference's host replay memory instead")
     ap.add_argument("--seconds", type=float, default=5.0)
     ap.add_argument("--merge", metavar="FILE", help="with --host: a device line to merge into")
+    ap.add_argument("--lib", metavar="SO", help="load this libtoricenv.so (another commit's build) instead of the tree's")
     a = ap.parse_args()
+    if a.lib:
+        from toric_rl_decoder_amd import _lib
+        _lib.LIB_PATH = os.path.abspath(a.lib)
     if a.targets:
         res = targets_part()
         print(json.dumps(res))

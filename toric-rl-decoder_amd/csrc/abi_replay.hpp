@@ -1,7 +1,6 @@
 // The replay memory's entry points of include/toricenv.h (part of toricenv.hip's translation unit: included there
 // after launch_scan, which the compaction of tq_replay_save_block shares with the environment).
 #pragma once
-#include <math.h>
 #include <stddef.h>
 
 #include <new>
@@ -26,10 +25,7 @@ struct tq_replay {                         // made by `new tq_replay()`: every m
 };
 
 namespace {
-int replay_levels(int64_t cap) {        // SumTree.tree_level: math.ceil(math.log(max_size+1, 2))+1
-    return (int)ceil(log((double)cap + 1.0) / log(2.0)) + 1;
-}
-double* leaves(const tq_replay* r) { return r->tree + ((int64_t(1) << (r->L - 1)) - 1); }
+double* leaves(const tq_replay* r) { return r->tree + tq::leaf_node(r->L, 0); }
 int replay_latch(int flag) {
     if (flag & tq::RP_ERR_UNDERFILLED) return fail(TQ_E_CAPACITY, "replay sample: fewer records filled than the batch size");
     if (flag & tq::RP_ERR_LEAF) return fail(TQ_E_INDEX, "replay sample: a draw ended on a leaf that holds no record");
@@ -47,7 +43,8 @@ static_assert(offsetof(tq::ReplayDev, werr) == offsetof(tq::ReplayDev, err) + si
 int replay_rebuild_all(tq_replay* r, hipStream_t stream) {
     hipLaunchKernelGGL(tq::k_replay_chunks, dim3((unsigned)r->nchunks), dim3(256), 0, stream, r->tree, r->L, r->clg,
                        r->nchunks, r->st, 0);
-    hipLaunchKernelGGL(tq::k_replay_top, dim3(1), dim3(1024), 0, stream, r->tree, r->L - 1 - r->clg, r->st, nullptr, r->cap);
+    hipLaunchKernelGGL(tq::k_replay_top, dim3(1), dim3(1024), 0, stream, r->tree, tq::chunk_root_level(r->L, r->clg), r->st,
+                       nullptr, r->cap);
     KCHECK();
     return TQ_OK;
 }
@@ -95,10 +92,10 @@ int tq_replay_create(tq_replay** out, int d, int64_t capacity, double alpha, int
     if (!r) return fail(TQ_E_INVALID, "out of host memory");
     r->d = d; r->w = (d * d + 63) / 64; r->device = device; r->faithful = faithful;
     r->cap = capacity; r->alpha = alpha; r->seed = seed;
-    r->L = replay_levels(capacity);
-    r->clg = r->L - 1 < tq::RP_CHUNK_LG ? r->L - 1 : tq::RP_CHUNK_LG;
-    r->nchunks = (capacity + (int64_t(1) << r->clg) - 1) >> r->clg;
-    r->mem.zeroed(&r->tree, ((size_t(1) << r->L) - 1) * sizeof(double));
+    r->L = tq::tree_levels(capacity);
+    r->clg = tq::chunk_lg(r->L);
+    r->nchunks = tq::chunk_count(capacity, r->clg);
+    r->mem.zeroed(&r->tree, (size_t)tq::tree_nodes(r->L) * sizeof(double));
     r->mem.zeroed(&r->ring, (size_t)tq::ring_bytes(r->w, capacity));
     r->mem.zeroed(&r->st, sizeof(tq::ReplayDev));
     r->mem.zeroed(&r->stamp, (size_t)capacity * sizeof(unsigned long long));
@@ -145,16 +142,10 @@ int tq_replay_save_block(tq_replay* r, const void* block, int64_t cap, void* str
     if (int rc = launch_scan(r->flags, r->partial, false, r->offsets, nullptr, cap, stream, nullptr)) return rc;
     hipLaunchKernelGGL(tq::k_replay_ingest, grid1(cap), dim3(BLOCK_1D), 0, stream, b, r->offsets, ring, r->w, leaves(r),
                        r->alpha, r->st);
-    // The touched positions start at the cursor and span at most min(cap, capacity), modulo the capacity.  Counted in
-    // chunk slots, a range that wraps also crosses the unused tail of the last chunk (nchunks * 2^clg - capacity
-    // leaves): so the chunks to rebuild are those of span + tail consecutive slots -- that many chunks and one more.
-    const int64_t span = cap < r->cap ? cap : r->cap;
-    const int64_t tail = (r->nchunks << r->clg) - r->cap;
-    int64_t nch = ((span + tail + (int64_t(1) << r->clg) - 1) >> r->clg) + 1;
-    if (nch > r->nchunks) nch = r->nchunks;
+    const int64_t nch = tq::chunks_to_rebuild(cap, r->cap, r->clg, r->nchunks);
     hipLaunchKernelGGL(tq::k_replay_chunks, dim3((unsigned)nch), dim3(256), 0, stream, r->tree, r->L, r->clg, r->nchunks,
                        r->st, 1);
-    hipLaunchKernelGGL(tq::k_replay_top, dim3(1), dim3(1024), 0, stream, r->tree, r->L - 1 - r->clg, r->st,
+    hipLaunchKernelGGL(tq::k_replay_top, dim3(1), dim3(1024), 0, stream, r->tree, tq::chunk_root_level(r->L, r->clg), r->st,
                        r->offsets + cap, r->cap);
     KCHECK();
     return TQ_OK;
@@ -260,7 +251,7 @@ int tq_replay_leaves(tq_replay* r, double* out, void* stream_) {
 
 int64_t tq_replay_tree_nodes(const tq_replay* r) {
     if (!r) return fail(TQ_E_INVALID, "NULL replay handle");
-    return (int64_t(1) << r->L) - 1;
+    return tq::tree_nodes(r->L);
 }
 
 int tq_replay_tree(tq_replay* r, double* out, void* stream_) {

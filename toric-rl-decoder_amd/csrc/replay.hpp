@@ -3,9 +3,9 @@
 // The semantics are those of the reference's PrioritizedReplayMemory / SumTree (src/ReplayMemory.py:45-152,
 // src/SumTree.py); the C-ABI (tq_replay_*) and the contract are in include/toricenv.h, the design in DESIGN.md §3.5.
 //
-// Tree: L levels (root = level 0), heap order, node n has children 2n+1 and 2n+2, leaf i is node 2^(L-1)-1+i and holds
-// record i.  Between calls every internal node is fl(left + right): no kernel adds into the tree with atomics, so the
-// tree is a function of its leaves.
+// Tree: L levels in heap order, leaf i holds record i; its index arithmetic, the geometry of the rebuild chunks and of
+// the sampler's segments, and the descent step are sum_tree.hpp's, for host and device.  Between calls every internal
+// node is fl(left + right): no kernel adds into the tree with atomics, so the tree is a function of its leaves.
 //   * ingest: flags (action word != 0) -> the project's two-level scan (scan.hpp) -> k_replay_ingest copies the
 //     non-empty slots in slot order to ring positions (cursor + k) % capacity and writes their leaves;
 //   * range rebuild: k_replay_chunks reduces 2048-leaf subtrees in LDS (one workgroup each, every internal node of the
@@ -21,12 +21,10 @@
 #include <stdint.h>
 
 #include "kernels.hpp"
+#include "sum_tree.hpp"
 
 namespace tq {
 
-constexpr int RP_CHUNK_LG = 11;          // leaves per range-rebuild workgroup: 2048 (16 KiB of f64, two LDS buffers)
-constexpr int RP_STAGE_LEVELS = 13;      // top levels of the tree staged in LDS by the sample kernel: 8191 nodes, 64 KiB
-constexpr int RP_SEG = 6;                // levels below the staged ones are fetched in subtrees of this depth (126 nodes)
 constexpr int RP_MAX_BATCH = 4096;       // draws per sample call: the pick list lives in LDS (48 KiB)
 constexpr int64_t RP_MAX_CAPACITY = int64_t(1) << 26;
 
@@ -104,21 +102,21 @@ __global__ __launch_bounds__(256) void k_replay_ingest(BlockView b, const int64_
 
 // ------------------------------------------------------------------ canonical rebuild
 // One workgroup per chunk of S = 2^clg leaves: every internal node of the chunk's subtree, from the leaves up to the
-// chunk root (level L-1-clg).  first_from_cursor: chunk (cursor >> clg) + blockIdx.x, modulo the `nchunks` chunks that
-// hold ring positions (the range an ingest touched starts at the cursor before it); otherwise chunk blockIdx.x.
+// chunk root.  first_from_cursor: chunk_of the cursor's chunk and blockIdx.x (the range an ingest touched starts at the
+// cursor before it); otherwise chunk blockIdx.x.
 // Rebuilding a canonical subtree changes nothing, so a chunk outside the touched range may be rebuilt too.
 __global__ __launch_bounds__(256) void k_replay_chunks(double* __restrict__ tree, int L, int clg, int64_t nchunks,
                                                        const ReplayDev* __restrict__ st, int first_from_cursor) {
     __shared__ double buf[2][1 << RP_CHUNK_LG];
     const int tid = threadIdx.x;
-    const int64_t c = first_from_cursor ? ((st->cursor >> clg) + blockIdx.x) % nchunks : (int64_t)blockIdx.x;
+    const int64_t c = first_from_cursor ? chunk_of(st->cursor >> clg, blockIdx.x, nchunks) : (int64_t)blockIdx.x;
     const int S = 1 << clg;
-    const int64_t leaf0 = ((int64_t)1 << (L - 1)) - 1 + c * S;
+    const int64_t leaf0 = leaf_node(L, c * S);
     for (int i = tid; i < S; i += 256) buf[0][i] = tree[leaf0 + i];
     __syncthreads();
     int src = 0, lvl = L - 2;
     for (int n = S >> 1; n >= 1; n >>= 1, --lvl) {
-        const int64_t base = ((int64_t)1 << lvl) - 1 + c * n;
+        const int64_t base = level_first(lvl) + c * n;
         for (int i = tid; i < n; i += 256) {
             const double v = buf[src][2 * i] + buf[src][2 * i + 1];
             buf[src ^ 1][i] = v;
@@ -135,8 +133,7 @@ __global__ __launch_bounds__(1024) void k_replay_top(double* __restrict__ tree, 
                                                      const int64_t* __restrict__ offsets_total, int64_t cap) {
     const int tid = threadIdx.x;
     for (int lvl = ltop - 1; lvl >= 0; --lvl) {
-        const int64_t n = (int64_t)1 << lvl;
-        for (int64_t i = tid; i < n; i += 1024) tree[n - 1 + i] = tree[2 * n - 1 + 2 * i] + tree[2 * n + 2 * i];
+        for (int64_t a = level_first(lvl) + tid; a < level_first(lvl + 1); a += 1024) tree[a] = tree[left_child(a)] + tree[left_child(a) + 1];
         rp_sync();
     }
     if (offsets_total && tid == 0) {
@@ -174,13 +171,12 @@ __global__ __launch_bounds__(256) void k_replay_scatter(const int64_t* __restric
 // is written by several threads, all with the same value
 __global__ __launch_bounds__(1024) void k_replay_paths(const int64_t* __restrict__ idx, int64_t n, double* __restrict__ tree, int L,
                                                        const ReplayDev* __restrict__ st) {
-    const int64_t nleaf = (int64_t)1 << (L - 1);
     for (int lvl = L - 2; lvl >= 0; --lvl) {
         for (int64_t j = threadIdx.x; j < n; j += 1024) {
             const int64_t i = idx[j];
             if (!rp_index_ok(i, st)) continue;
-            const int64_t a = ((nleaf + i) >> (L - 1 - lvl)) - 1;
-            tree[a] = tree[2 * a + 1] + tree[2 * a + 2];
+            const int64_t a = ancestor_at(L, i, lvl), lc = left_child(a);
+            tree[a] = tree[lc] + tree[lc + 1];
         }
         rp_sync();
     }
@@ -209,102 +205,45 @@ __global__ __launch_bounds__(256) void k_replay_realpha(double* __restrict__ lea
 // Wave 0 draws (its values are wave-uniform); the whole workgroup stages the tree and computes the weights.
 // u: caller's uniforms f64[B], or NULL: Philox4x32-10 keyed by `seed`, counter (call lo, call hi, 0, 5<<24 | k),
 // u = ((w0>>5)*2^26 + (w1>>6)) * 2^-53 (Python's random.random construction).
-__global__ __launch_bounds__(256) void k_replay_sample(const double* __restrict__ tree, int L, int64_t cap, int B, double beta,
-                                                       const double* __restrict__ u, uint64_t seed, uint64_t call,
-                                                       int64_t* __restrict__ idx_out, double* __restrict__ prio_out,
-                                                       double* __restrict__ w_out, ReplayDev* __restrict__ st) {
-    __shared__ double stg[(1 << RP_STAGE_LEVELS) - 1];
-    __shared__ double pv[RP_MAX_BATCH];
-    __shared__ int32_t pleaf[RP_MAX_BATCH];
-    __shared__ double seg[(2 << RP_SEG) - 2];
-    __shared__ double wred[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t filled = st->filled;
-    if (filled < B) {                               // the reference returns (None, None, None) (:108-109)
-        if (tid == 0) atomicOr(&st->err, RP_ERR_UNDERFILLED);
-        for (int k = tid; k < B; k += 256) { idx_out[k] = -1; prio_out[k] = 0.0; w_out[k] = 0.0; }
-        return;
-    }
-    const int T = L < RP_STAGE_LEVELS ? L : RP_STAGE_LEVELS;
-    const int64_t nleaf = (int64_t)1 << (L - 1);
-    for (int i = tid; i < (1 << T) - 1; i += 256) stg[i] = tree[i];
-    __syncthreads();
-    if (wave == 0) {
-        for (int k = 0; k < B; ++k) {
-            double value;
-            if (u) {
-                value = u[k];
-            } else {
-                const U4 w = philox4x32_10((uint32_t)call, (uint32_t)(call >> 32), 0u, (DOMAIN_REPLAY << 24) | (uint32_t)k,
-                                           (uint32_t)seed, (uint32_t)(seed >> 32));
-                value = ((double)(w.x >> 5) * 67108864.0 + (double)(w.y >> 6)) * (1.0 / 9007199254740992.0);
-            }
-            value = value * stg[0];
-            int64_t node = 0;
-            int lvl = 0;
-            double cur = stg[0];
-            for (; lvl < T - 1; ++lvl) {
-                const int64_t lc = 2 * node + 1;
-                const double left = stg[lc];
-                if (value <= left) { node = lc; cur = left; }
-                else { value = value - left; node = lc + 1; cur = stg[lc + 1]; }
-            }
-            while (lvl < L - 1) {
-                const int depth = L - 1 - lvl < RP_SEG ? L - 1 - lvl : RP_SEG;
-                const int nseg = (2 << depth) - 2;
-                for (int t = lane; t < nseg; t += 64) {
-                    const int r = 31 - __clz(t + 2);
-                    seg[t] = tree[((node + 1) << r) - 1 + (t + 2 - (1 << r))];
-                }
-                rp_wave_sync();
-                const int below = L - 1 - lvl;                              // leaf levels under `node`
-                const int64_t first = ((node + 1) << below) - nleaf;        // its first leaf
-                for (int c0 = 0; c0 < k; c0 += 64) {
-                    const int j = c0 + lane;
-                    const bool hit = j < k && (int64_t)pleaf[j] - first >= 0 && (int64_t)pleaf[j] - first < ((int64_t)1 << below);
-                    uint64_t mask = __ballot(hit);
-                    while (mask) {
-                        const int bit = __ffsll((unsigned long long)mask) - 1;
-                        mask &= mask - 1;
-                        const int jj = c0 + bit;
-                        const int64_t rel = (int64_t)pleaf[jj] - first;
-                        const double v = pv[jj];
-                        if (lane < depth) {                                 // lane r-1: the ancestor r levels down
-                            const int r = lane + 1;
-                            const int q = (int)(rel >> (below - r));
-                            seg[(1 << r) - 2 + q] = seg[(1 << r) - 2 + q] - v;
-                        }
-                        rp_wave_sync();
-                    }
-                }
-                int q = 0;
-                for (int r = 1; r <= depth; ++r) {
-                    const int lc = (1 << r) - 2 + 2 * q;
-                    const double left = seg[lc];
-                    if (value <= left) { q = 2 * q; cur = left; }
-                    else { value = value - left; q = 2 * q + 1; cur = seg[lc + 1]; }
-                }
-                node = ((node + 1) << depth) - 1 + q;
-                lvl += depth;
-                rp_wave_sync();                                             // seg is reloaded by the next segment
-            }
-            const int64_t leaf = node - (nleaf - 1);
-            if (lane == 0) {
-                pleaf[k] = (int32_t)leaf;
-                pv[k] = cur;
-                idx_out[k] = leaf;
-                prio_out[k] = cur;
-                if (leaf >= filled) atomicOr(&st->err, RP_ERR_LEAF);
-            }
-            if (lane < T) {                                                 // staged ancestors (distinct nodes)
-                const int64_t a = ((nleaf + leaf) >> (L - 1 - lane)) - 1;
-                stg[a] = stg[a] - cur;
-            }
+//
+// The steps of one draw (wave 0, every value wave-uniform) that are plain arithmetic are sum_tree.hpp's: descend_staged,
+// seg_fetch, seg_walk, and one lane's share of the two below.  The draw's uniform in [0, 1):
+__device__ __forceinline__ double rp_uniform(const double* __restrict__ u, uint64_t seed, uint64_t call, int k) {
+    if (u) return u[k];
+    const U4 w = philox4x32_10((uint32_t)call, (uint32_t)(call >> 32), 0u, (DOMAIN_REPLAY << 24) | (uint32_t)k, (uint32_t)seed,
+                               (uint32_t)(seed >> 32));
+    return ((double)(w.x >> 5) * 67108864.0 + (double)(w.y >> 6)) * (1.0 / 9007199254740992.0);
+}
+// Of the k earlier picks those under `node` (of level lvl) off the fetched segment, in pick order.
+__device__ __forceinline__ void rp_seg_apply_picks(double* seg, const int32_t* pleaf, const double* pv, int k, int L, int64_t node,
+                                                   int lvl, int depth, int lane) {
+    for (int c0 = 0; c0 < k; c0 += 64) {
+        uint64_t mask = __ballot(c0 + lane < k && leaf_under(L, pleaf[c0 + lane], node, lvl));
+        while (mask) {
+            const int j = c0 + __ffsll((unsigned long long)mask) - 1;
+            mask &= mask - 1;
+            seg_apply_pick(seg, L, node, lvl, depth, pleaf[j], pv[j], lane);
             rp_wave_sync();
         }
     }
-    __syncthreads();
-    // weights (1/capacity/priority)^beta, 0 for priority <= 1e-16, normalised by their maximum (:112-121)
+}
+// The pick of draw k: into the pick list and the outputs, and off its staged ancestors.
+__device__ __forceinline__ void rp_record_pick(double* stg, double* pv, int32_t* pleaf, int k, int L, int T, int64_t leaf, double cur,
+                                               int64_t filled, int64_t* __restrict__ idx_out, double* __restrict__ prio_out,
+                                               ReplayDev* __restrict__ st, int lane) {
+    if (lane == 0) {
+        pleaf[k] = (int32_t)leaf;
+        pv[k] = cur;
+        idx_out[k] = leaf;
+        prio_out[k] = cur;
+        if (leaf >= filled) atomicOr(&st->err, RP_ERR_LEAF);
+    }
+    stage_correct(stg, L, T, leaf, cur, lane);
+}
+// The weights of the B picks (whole workgroup): (1/capacity/priority)^beta, 0 for priority <= 1e-16, normalised by
+// their maximum (:112-121); pv holds the priorities and is overwritten.
+__device__ __forceinline__ void rp_weights(double* pv, double* wred, int B, int64_t cap, double beta, double* __restrict__ w_out) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double wmax = 0.0;
     for (int k = tid; k < B; k += 256) {
         const double p = pv[k];
@@ -318,6 +257,46 @@ __global__ __launch_bounds__(256) void k_replay_sample(const double* __restrict_
     wmax = wred[0];
     for (int i = 1; i < 4; ++i) wmax = wred[i] > wmax ? wred[i] : wmax;
     for (int k = tid; k < B; k += 256) w_out[k] = wmax > 0.0 ? pv[k] / wmax : 0.0;   // all zero: the reference raises
+}
+
+__global__ __launch_bounds__(256) void k_replay_sample(const double* __restrict__ tree, int L, int64_t cap, int B, double beta,
+                                                       const double* __restrict__ u, uint64_t seed, uint64_t call,
+                                                       int64_t* __restrict__ idx_out, double* __restrict__ prio_out,
+                                                       double* __restrict__ w_out, ReplayDev* __restrict__ st) {
+    __shared__ double stg[tree_nodes(RP_STAGE_LEVELS)];
+    __shared__ double pv[RP_MAX_BATCH];
+    __shared__ int32_t pleaf[RP_MAX_BATCH];
+    __shared__ double seg[seg_words(RP_SEG)];
+    __shared__ double wred[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t filled = st->filled;
+    if (filled < B) {                               // the reference returns (None, None, None) (:108-109)
+        if (tid == 0) atomicOr(&st->err, RP_ERR_UNDERFILLED);
+        for (int k = tid; k < B; k += 256) { idx_out[k] = -1; prio_out[k] = 0.0; w_out[k] = 0.0; }
+        return;
+    }
+    const int T = staged_levels(L);
+    for (int i = tid; i < (int)tree_nodes(T); i += 256) stg[i] = tree[i];
+    __syncthreads();
+    if (wave == 0) {
+        for (int k = 0; k < B; ++k) {
+            double value = rp_uniform(u, seed, call, k) * stg[0], cur = stg[0];
+            int64_t node = descend_staged(stg, T, value, cur);
+            for (int lvl = T - 1; lvl < L - 1;) {
+                const int depth = seg_depth(L, lvl);
+                seg_fetch(seg, tree, node, depth, lane);
+                rp_wave_sync();
+                rp_seg_apply_picks(seg, pleaf, pv, k, L, node, lvl, depth, lane);
+                node = seg_child_node(node, depth, seg_walk(seg, depth, value, cur));
+                lvl += depth;
+                rp_wave_sync();                                             // seg is reloaded by the next segment
+            }
+            rp_record_pick(stg, pv, pleaf, k, L, T, leaf_of_node(L, node), cur, filled, idx_out, prio_out, st, lane);
+            rp_wave_sync();
+        }
+    }
+    __syncthreads();
+    rp_weights(pv, wred, B, cap, beta, w_out);
 }
 
 // ------------------------------------------------------------------ gather
