@@ -411,6 +411,46 @@ int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* bi
  * before the first tq_nn11_load. */
 int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
 
+/* ---- NN_11's learner step (src/Learner_mp.py:140-169): the forward with every layer's output kept, the gather of
+ * Q(s,a), the weighted squared error, the backward pass and the parameter gradients.  The optimizer stays the caller's and
+ * works on its f32 master parameters.  Design: DESIGN.md 3.7.
+ * Numerics contract.  The forward is tq_nn11_forward's: A_0 is the stack converted to bf16, A_l (l = 1..11) the layers'
+ * bf16 outputs, q is f32 and bit-equal to tq_nn11_forward on the same weights and rows.
+ *  Head, per record i with a = actions_idx[i], all in f32, each operation rounded once, left to right, nothing contracted:
+ *   - e = y[i] - q[i][a];  loss[i] = w[i] * (e * e)  (the reference takes |loss[i]| as the record's new priority);
+ *   - dq[i][a] = (((q[i][a] - y[i]) * w[i]) * 2) / (float)n, the row's other two entries 0: the gradient of
+ *     mean_i(loss[i]) (Learner_mp.py:152-160);  w == NULL means all ones;
+ *   - actions_idx[i] outside 0..2: loss[i] = 0, dq[i] = 0, and TQ_E_ACTION is latched (tq_nn11_grad_check).
+ *  Gradients of the pre-activations, G_l for layer l, stored as bf16 (RNE; bf16 has f32's exponent range: no loss scaling):
+ *   - the ReLU mask is A_l > 0 on the stored bf16 activation;
+ *   - G_11 = bf16(mask_11 * sum_a dq[.][a] * Wlin_bf16[a][.]);
+ *   - l = 11..2: G_{l-1} = bf16(mask_{l-1} * conv_transpose(G_l, W_l rounded to bf16)), accumulated in f32; conv11 is
+ *     unpadded, so its transpose is a full correlation from the (d-2)^2 grid onto the d^2 grid;
+ *   - no gradient is formed for the stack.
+ *  Parameter gradients, f32 in torch layout, written (not accumulated):
+ *   - dW_l[co][ci][ky][kx] = sum over records and pixels of G_l * A_{l-1}(shifted by the tap; conv1: with the circular
+ *     wrap), bf16 x bf16 products accumulated in f32;  db_l = sum G_l;
+ *   - dWlin = dq^T A_11 in torch's (channel, y, x) feature order;  dblin = sum_i dq[i];
+ *   - these are gradients at the bf16-rounded weights, to be applied to the f32 masters (straight-through).
+ *  Determinism: no atomics in any sum; how a sum is cut into partial sums depends on (d, n) alone, never on occupancy or
+ *  timing: the same call gives the same bits.  A padded channel's G is 0 because its mask is 0.
+ * One handle, one stream, as for tq_nn11_*: create / destroy allocate and synchronise, load and step only enqueue. */
+typedef struct tq_nn11_grad tq_nn11_grad;
+/* Allocates both weight images, the eleven activation images (each of its layer's own padded channel count), two gradient
+ * images and the wgrad partial images for steps of up to max_batch (1..4096) records. */
+int tq_nn11_grad_create(tq_nn11_grad** out, int d, int max_batch, int device);
+int tq_nn11_grad_destroy(tq_nn11_grad* h);
+/* weights / biases as for tq_nn11_load; packs the forward and the dgrad images on the device. */
+int tq_nn11_grad_load(tq_nn11_grad* h, const float* const* weights, const float* const* biases, void* stream);
+/* One step on state[n][2][d][d] (element type dtype, 16-byte aligned): actions_idx i64[n] in 0..2, y f32[n], w f32[n] or
+ * NULL -> q f32[n][3] (may be NULL), loss f32[n], and the gradients into grad_w[12] / grad_b[12], HOST arrays of device
+ * pointers to f32 tensors in the layout of tq_nn11_load's.  Checked before any launch (TQ_E_INVALID): n outside
+ * 1..max_batch, a NULL pointer, a misaligned state, a call before the first load. */
+int tq_nn11_grad_step(tq_nn11_grad* h, const void* state, int dtype, int n, const int64_t* actions_idx, const float* y,
+                      const float* w, float* q, float* loss, float* const* grad_w, float* const* grad_b, void* stream);
+/* Reads and clears the handle's device error latch (synchronises `stream`): 0 or TQ_E_ACTION. */
+int tq_nn11_grad_check(tq_nn11_grad* h, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

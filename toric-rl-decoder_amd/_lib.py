@@ -88,6 +88,11 @@ SYMBOLS = [
     ("tq_nn11_destroy", _i, [_vp]),
     ("tq_nn11_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     ("tq_nn11_forward", _i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    ("tq_nn11_grad_create", _i, [C.POINTER(_vp), _i, _i, _i]),
+    ("tq_nn11_grad_destroy", _i, [_vp]),
+    ("tq_nn11_grad_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("tq_nn11_grad_step", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("tq_nn11_grad_check", _i, [_vp, _vp]),
 ]
 
 _lib = None

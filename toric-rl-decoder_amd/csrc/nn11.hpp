@@ -30,7 +30,8 @@ constexpr int NN11_CH[NN11_LAYERS + 1] = {2, 128, 128, 120, 111, 104, 103, 90, 8
 constexpr int NN11_OUT = 3;                 // Q-values per perspective
 constexpr int NN11_MAX_CP = 128;
 
-enum { NN11_CIRCULAR = 0, NN11_ZERO = 1, NN11_VALID = 2 };
+enum { NN11_CIRCULAR = 0, NN11_ZERO = 1, NN11_VALID = 2, NN11_FULL = 3 };   // NN11_FULL: the backward of NN11_VALID
+enum { NN11_EPI_BIAS_RELU = 0, NN11_EPI_MASK = 1 };                       // what k_nn11_conv does with its sums
 
 TQ_HD int nn11_cpad(int c) { return (c + 31) & ~31; }
 // layer l = 1..11
@@ -77,6 +78,9 @@ TQ_HD float nn11_f32(uint16_t b) {
 #endif
 }
 
+// the ReLU mask of the backward pass: a stored bf16 activation is > 0 (activations are never negative or NaN)
+TQ_HD bool nn11_mask(uint16_t a) { return a != 0 && !(a & 0x8000u); }
+
 // ---- weight image of one layer: element <-> (cout, k, tap)
 TQ_HD int64_t nn11_wimg_index(int tap, int kstep, int ntile, int lane, int j, int ksteps, int ntiles) {
     return ((((int64_t)tap * ksteps + kstep) * ntiles + ntile) * 64 + lane) * 8 + j;
@@ -103,6 +107,23 @@ TQ_HD float nn11_wimg_value(int l, int64_t idx, const float* w) {
     return w[((int64_t)c.cout * nn11_cin(l) + c.k) * 9 + c.tap];
 }
 
+// ---- dgrad weight image of layer l = 2..11: the image of the convolution that takes G_l (cout(l) channels) to the
+// gradient of layer l - 1's output (cin(l) channels).  Same fragment order with the two channel counts in each other's
+// place and the taps flipped: element (cout' = ci, k = co, tap') = W_l[co][ci][8 - tap'].
+TQ_HD int nn11_dksteps(int l) { return nn11_cpad(nn11_cout(l)) / 16; }
+TQ_HD int nn11_dntiles(int l) { return nn11_cpad(nn11_cin(l)) / 32; }
+TQ_HD int64_t nn11_dimg_elems(int l) { return (int64_t)9 * nn11_dksteps(l) * nn11_dntiles(l) * 512; }
+TQ_HD int64_t nn11_dimg_offset(int l) {            // first element of layer l = 2..12 in the handle's one dgrad image
+    int64_t o = 0;
+    for (int i = 2; i < l; ++i) o += nn11_dimg_elems(i);
+    return o;
+}
+TQ_HD float nn11_dimg_value(int l, int64_t idx, const float* w) {
+    const NN11WCoord c = nn11_wimg_coord(idx, nn11_dksteps(l), nn11_dntiles(l));       // .cout: ci, .k: co
+    if (c.cout >= nn11_cin(l) || c.k >= nn11_cout(l)) return 0.f;
+    return w[((int64_t)c.k * nn11_cin(l) + c.cout) * 9 + (8 - c.tap)];
+}
+
 // ---- linear image [a][pixel][64] <- torch [a][c * npix + pixel]
 TQ_HD int64_t nn11_lin_index(int a, int pixel, int c, int npix) { return ((int64_t)a * npix + pixel) * 64 + c; }
 TQ_HD float nn11_lin_value(int64_t idx, int npix, const float* w) {
@@ -115,9 +136,15 @@ TQ_HD float nn11_lin_value(int64_t idx, int npix, const float* w) {
 TQ_HD int64_t nn11_act_index(int64_t persp, int pixel, int c, int npix, int cp) { return (persp * npix + pixel) * cp + c; }
 
 // ---- tap -> source pixel.  (y, x): the OUTPUT pixel in its own grid (d x d; (d-2) x (d-2) for NN11_VALID); tap =
-// 3 ky + kx.  -> pixel index in the d x d input grid, or -1 for the zero padding.
+// 3 ky + kx.  -> pixel index in the d x d input grid, or -1 for the zero padding.  NN11_FULL is the transpose of
+// NN11_VALID (a full correlation): the output grid is d x d, the input grid (d-2) x (d-2), and the source of tap
+// (ky, kx) is (y + ky - 2, x + kx - 2) where that lies inside it.
 TQ_HD int nn11_src_pixel(int mode, int d, int y, int x, int tap) {
     int sy = y + tap / 3 - 1, sx = x + tap % 3 - 1;
+    if (mode == NN11_FULL) {
+        sy -= 1; sx -= 1;
+        return (sy < 0 || sy >= d - 2 || sx < 0 || sx >= d - 2) ? -1 : sy * (d - 2) + sx;
+    }
     if (mode == NN11_VALID) { sy += 1; sx += 1; }
     else if (mode == NN11_CIRCULAR) {
         sy = sy < 0 ? sy + d : (sy >= d ? sy - d : sy);
@@ -149,6 +176,10 @@ inline void nn11_pack_layer_host(int l, const float* w, const float* b, uint16_t
     for (int64_t i = 0; i < n; ++i) wimg[i] = nn11_bf16(nn11_wimg_value(l, i, w));
     const int cp = nn11_cpad(nn11_cout(l));
     for (int c = 0; c < cp; ++c) bias[c] = c < nn11_cout(l) ? b[c] : 0.f;
+}
+inline void nn11_pack_dgrad_host(int l, const float* w, uint16_t* dimg) {       // l = 2..11
+    const int64_t n = nn11_dimg_elems(l);
+    for (int64_t i = 0; i < n; ++i) dimg[i] = nn11_bf16(nn11_dimg_value(l, i, w));
 }
 inline void nn11_pack_linear_host(int d, const float* w, float* limg) {
     const int64_t n = nn11_lin_elems(d);
@@ -193,14 +224,18 @@ __device__ __forceinline__ uint16_t nn11_stack_bf16(const void* stack, int dtype
 // NT: tiles of 32 output channels, MODE: where a tap's source pixel lies.  `in`: the previous layer's activation image
 // (MODE != CIRCULAR) or the perspective stack [P][2][d][d] of element type `dtype`; `out`: this layer's activation image
 // ((d-2)^2 pixels for NN11_VALID).  Grid: ceil(P / G) workgroups of NN11Geom<D>::THREADS threads.
-template <int D, int KS, int NT, int MODE>
+// EPI says what becomes of the sums.  NN11_EPI_BIAS_RELU (the forward): `aux` is the layer's padded f32 bias;
+// out = bf16(relu(sum + bias)).  NN11_EPI_MASK (the backward's dgrad over a dgrad image; NN11_FULL reads a (d-2)^2
+// image): `aux` is the bf16 activation image of `out`'s shape; out = bf16(sum where the activation is > 0, else 0).
+template <int D, int KS, int NT, int MODE, int EPI = NN11_EPI_BIAS_RELU>
 __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nn11_conv(const void* __restrict__ in, int dtype, const uint16_t* __restrict__ wimg,
-                                                   const float* __restrict__ bias, uint16_t* __restrict__ out, int64_t P) {
+                                                   const void* __restrict__ aux, uint16_t* __restrict__ out, int64_t P) {
     using Ge = NN11Geom<D>;
     constexpr int PIX = Ge::PIX, G = Ge::G, MW = Ge::MW, NW = Ge::NW, THREADS = Ge::THREADS;
     constexpr int NPIX_OUT = MODE == NN11_VALID ? Ge::OPIX : PIX;
     constexpr int OD = MODE == NN11_VALID ? D - 2 : D;                      // side of the output grid
     constexpr int ROWS_OUT = G * NPIX_OUT;
+    constexpr int NPIX_IN = MODE == NN11_FULL ? Ge::OPIX : PIX;             // pixels of one perspective in `in`
     constexpr int CINP = KS * 16, COUTP = NT * 32;
     // LDS: the workgroup's input rows, channels last, 16 bytes of padding per row (consecutive rows start in different
     // banks: the 16-byte fragment reads of 8 neighbouring pixels are conflict-free); conv1 stages its G x 2 x d^2 stack
@@ -218,11 +253,11 @@ __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nn11_conv(const void* 
         for (int i = tid; i < G * 2 * PIX; i += THREADS)
             s[i] = i < np * 2 * PIX ? nn11_stack_bf16(in, dtype, persp0 * 2 * PIX + i) : (uint16_t)0;
     } else {
-        const uint4* src = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(in) + persp0 * PIX * CINP);
+        const uint4* src = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(in) + persp0 * NPIX_IN * CINP);
         constexpr int CH16 = CINP / 8;                                      // 16-byte chunks per row
         for (int c = tid; c < Ge::LROWS * CH16; c += THREADS) {
             const int row = c / CH16, cc = c % CH16;
-            const uint4 v = row < np * PIX ? src[c] : make_uint4(0, 0, 0, 0);
+            const uint4 v = row < np * NPIX_IN ? src[c] : make_uint4(0, 0, 0, 0);
             *reinterpret_cast<uint4*>(lds + row * PITCH + cc * 16) = v;
         }
     }
@@ -236,7 +271,7 @@ __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nn11_conv(const void* 
         const int row = (NW * i + wave) * 32 + r;
         const int p = row / NPIX_OUT, q = row % NPIX_OUT;
         py[i] = q / OD; px[i] = q % OD;
-        pbase[i] = row < ROWS_OUT ? p * PIX : -1;
+        pbase[i] = row < ROWS_OUT ? p * NPIX_IN : -1;
     }
 
     nn11_f32x16 acc[MW][NT];
@@ -311,9 +346,16 @@ __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nn11_conv(const void* 
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
                 const int c0 = 32 * n + 8 * g + 4 * h;
-                const float4 b = *reinterpret_cast<const float4*>(bias + c0);
-                const float v0 = fmaxf(acc[i][n][4 * g + 0] + b.x, 0.f), v1 = fmaxf(acc[i][n][4 * g + 1] + b.y, 0.f);
-                const float v2 = fmaxf(acc[i][n][4 * g + 2] + b.z, 0.f), v3 = fmaxf(acc[i][n][4 * g + 3] + b.w, 0.f);
+                float v0, v1, v2, v3;
+                if constexpr (EPI == NN11_EPI_BIAS_RELU) {
+                    const float4 b = *reinterpret_cast<const float4*>(static_cast<const float*>(aux) + c0);
+                    v0 = fmaxf(acc[i][n][4 * g + 0] + b.x, 0.f); v1 = fmaxf(acc[i][n][4 * g + 1] + b.y, 0.f);
+                    v2 = fmaxf(acc[i][n][4 * g + 2] + b.z, 0.f); v3 = fmaxf(acc[i][n][4 * g + 3] + b.w, 0.f);
+                } else {                                                    // bf16 > 0: sign clear and not a zero
+                    const uint2 m = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(aux) + (persp0 * NPIX_OUT + row) * COUTP + c0);
+                    v0 = nn11_mask((uint16_t)m.x) ? acc[i][n][4 * g + 0] : 0.f; v1 = nn11_mask((uint16_t)(m.x >> 16)) ? acc[i][n][4 * g + 1] : 0.f;
+                    v2 = nn11_mask((uint16_t)m.y) ? acc[i][n][4 * g + 2] : 0.f; v3 = nn11_mask((uint16_t)(m.y >> 16)) ? acc[i][n][4 * g + 3] : 0.f;
+                }
                 uint2 pk;
                 pk.x = (uint32_t)nn11_bf16(v0) | ((uint32_t)nn11_bf16(v1) << 16);
                 pk.y = (uint32_t)nn11_bf16(v2) | ((uint32_t)nn11_bf16(v3) << 16);

@@ -11,6 +11,8 @@ hand-written HIP (csrc/nn11.hpp behind tq_nn11_*): NN11Forward wraps a model's w
   learnerTargets       src/Learner_mp.py:146-151 (targets straight from the device replay memory)
   evaluate             src/evaluation.py:10-124
   NN11Forward          src/nn/torch/NN.py:10-45, src/nn/torch/util.py:21-26 (the forward as bf16 MFMA kernels)
+  NN11Grad             src/Learner_mp.py:140-160 (forward, loss head and backward pass as HIP kernels)
+  learnerStep          src/Learner_mp.py:135-169 (one learner iteration on a device replay memory)
 """
 import ctypes as C
 
@@ -108,6 +110,94 @@ class NN11Forward(Handle):
 
     def to(self, *args, **kwargs):                         # evaluate() moves its model to the device: it is there already
         return self
+
+
+_NN11_NAMES = [f"conv{i + 1}" for i in range(11)] + ["linear1"]
+
+
+class NN11Grad(Handle):
+    """NN_11's learner step as HIP kernels (tq_nn11_grad_*; numerics contract in include/toricenv.h): the forward with
+    every layer kept, the gather of Q(s,a), the weighted squared error and the backward pass, bf16 operands with f32
+    accumulation.  ``model``: a torch NN_11 on ``device`` whose f32 parameters are the masters -- ``backward`` fills their
+    ``.grad`` (written, not accumulated), the caller's optimizer steps them, ``load()`` re-reads them.  One handle, one
+    stream; ``max_batch`` (1..4096) sizes the scratch."""
+
+    _destroy = "tq_nn11_grad_destroy"
+
+    def __init__(self, model, system_size, device, max_batch=256):
+        self.device = require_gpu(device)
+        self.system_size = int(system_size)
+        self.max_batch = int(max_batch)
+        self.model = model
+        ch, feats = NN_11.CHANNELS, 64 * (self.system_size - 2) ** 2
+        shapes = [(ch[i + 1], ch[i], 3, 3) for i in range(11)] + [(3, feats)]
+        self._params = []
+        for n, shape in zip(_NN11_NAMES, shapes):
+            m = getattr(model, n)
+            for p, want in ((m.weight, shape), (m.bias, shape[:1])):
+                if tuple(p.shape) != want or p.dtype != torch.float32 or p.device != self.device or not p.is_contiguous():
+                    raise ValueError(f"{n}: expected contiguous float32 {want} on {self.device}, got {p.dtype} {tuple(p.shape)} on {p.device}")
+            self._params.append((m.weight, m.bias))
+        self._L = _lib.load()
+        self._h = C.c_void_p(None)
+        check(self._L.tq_nn11_grad_create(C.byref(self._h), self.system_size, self.max_batch, self.device.index))
+        self.load()
+
+    def load(self):
+        """Re-reads the model's parameters (packed on the device, no allocation): after every optimizer step."""
+        wp = (C.c_void_p * 12)(*[w.data_ptr() for w, _ in self._params])
+        bp = (C.c_void_p * 12)(*[b.data_ptr() for _, b in self._params])
+        self._call(self._L.tq_nn11_grad_load, wp, bp)
+        return self
+
+    def backward(self, state, actions_idx, y, weights=None):
+        """Learner_mp.py:140-160 for one batch: ``state`` (n, 2, d, d) float32 / float16 / bfloat16 / uint8,
+        ``actions_idx`` int64 (n,) in 0..2, ``y`` the targets, ``weights`` the importance weights (None: ones) ->
+        (loss f32 (n,) = weights * (y - Q(s,a))^2, q f32 (n, 3)); every parameter's ``.grad`` holds the gradient of
+        loss.mean().  An action outside 0..2 gets loss 0 and no gradient, and check() raises for it."""
+        if state.dtype not in _STACK_DTYPES:
+            raise ValueError(f"state dtype {state.dtype} not one of float32 / float16 / bfloat16 / uint8")
+        d, dev = self.system_size, self.device
+        if state.dim() != 4 or tuple(state.shape[1:]) != (2, d, d) or state.device != dev:
+            raise ValueError(f"expected a (n, 2, {d}, {d}) state on {dev}, got {tuple(state.shape)} on {state.device}")
+        n = state.shape[0]
+        state = state.contiguous()
+        a = to_device(actions_idx, torch.int64, dev).reshape(-1)
+        y = to_device(y.detach() if torch.is_tensor(y) else y, torch.float32, dev).reshape(-1)
+        w = None if weights is None else to_device(weights, torch.float32, dev).reshape(-1)
+        if a.numel() != n or y.numel() != n or (w is not None and w.numel() != n):
+            raise ValueError("actions_idx / y / weights must have one entry per record")
+        for wt, bt in self._params:
+            for p in (wt, bt):
+                if p.grad is None or not p.grad.is_contiguous():
+                    p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
+        q = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        loss = torch.empty(n, dtype=torch.float32, device=dev)
+        gw = (C.c_void_p * 12)(*[wt.grad.data_ptr() for wt, _ in self._params])
+        gb = (C.c_void_p * 12)(*[bt.grad.data_ptr() for _, bt in self._params])
+        self._call(self._L.tq_nn11_grad_step, _ptr(state), _STACK_DTYPES[state.dtype], n, _ptr(a), _ptr(y), _ptr(w), _ptr(q),
+                   _ptr(loss), gw, gb)
+        return loss, q
+
+    def check(self):
+        """Reads and clears the device error latch (synchronises): ValueError for an action outside 0..2."""
+        self._call(self._L.tq_nn11_grad_check)
+
+
+def learnerStep(grad, target_model, memory, optimizer, batch_size, beta, discount=0.95, batch=None):
+    """One iteration of Learner_mp.py:135-169 on a device PrioritizedReplayMemory: sample_batch -> learnerTargets on
+    ``target_model`` (a torch module or an NN11Forward) -> ``grad.backward`` -> ``optimizer.step()`` on the masters ->
+    ``grad.load()`` -> priority_update(indices, |loss|).  ``batch``: a sample_batch result to step on instead of drawing
+    one (its next_state is not used).  -> (loss f32 (B,), indices i64 (B,)) device tensors."""
+    if batch is None:
+        batch = memory.sample_batch(batch_size, beta, next_state=False)
+    state, actions, reward, _, terminal, weights, indices = batch
+    y = learnerTargets(target_model, memory, indices, reward, terminal, discount=discount)
+    loss, _ = grad.backward(state, actions, y, weights)
+    optimizer.step()
+    grad.load()
+    memory.update_priorities(indices, loss.abs())
+    return loss, indices
 
 
 def _forward_chunked(model, persp, chunk, pad_to=1024, backing=None, out=None):
