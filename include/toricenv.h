@@ -412,8 +412,8 @@ int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* bi
 int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
 
 /* ---- NN_11's learner step (src/Learner_mp.py:140-169): the forward with every layer's output kept, the gather of
- * Q(s,a), the weighted squared error, the backward pass and the parameter gradients.  The optimizer stays the caller's and
- * works on its f32 master parameters.  Design: DESIGN.md 3.7.
+ * Q(s,a), the weighted squared error, the backward pass and the parameter gradients.  The optimizer works on the caller's
+ * f32 master parameters: the caller's own, or tq_nn11_grad_opt_step below.  Design: DESIGN.md 3.7.
  * Numerics contract.  The forward is tq_nn11_forward's: A_0 is the stack converted to bf16, A_l (l = 1..11) the layers'
  * bf16 outputs, q is f32 and bit-equal to tq_nn11_forward on the same weights and rows.
  *  Head, per record i with a = actions_idx[i], all in f32, each operation rounded once, left to right, nothing contracted:
@@ -450,6 +450,47 @@ int tq_nn11_grad_step(tq_nn11_grad* h, const void* state, int dtype, int n, cons
                       const float* w, float* q, float* loss, float* const* grad_w, float* const* grad_b, void* stream);
 /* Reads and clears the handle's device error latch (synchronises `stream`): 0 or TQ_E_ACTION. */
 int tq_nn11_grad_check(tq_nn11_grad* h, void* stream);
+
+/* ---- NN_11's optimizer step (src/Learner_mp.py:81-84: Adam or RMSprop on the f32 masters) in one launch: reads the
+ * gradients tq_nn11_grad_step wrote, updates the masters and the optimizer state in place and, from the same registers,
+ * rewrites the handle's bf16 forward image, dgrad image, biases and linear image, so that no tq_nn11_grad_load follows.
+ * Design: DESIGN.md 3.8.
+ * Numerics contract.  Per element, all in f32, each operation rounded once in the order the parentheses give, nothing
+ * contracted; sqrt and / are IEEE correctly rounded (hipcc's default for f32, which the contract relies on) and subnormals
+ * are kept.  NaN and Inf propagate as IEEE has it; nothing is clamped.
+ *  Scalars: computed on the host in double as Python does (b^t is pow), each cast to f32 once; t = step, the 1-based count
+ *  of this update.
+ *  TQ_OPT_ADAM:  c1 = (float)(1 - beta1), c2 = (float)beta2, c3 = (float)(1 - beta2), cb = (float)sqrt(1 - beta2^t),
+ *   ce = (float)eps, cs = (float)(-(lr / (1 - beta1^t)))
+ *   - m' = m + c1 * (g - m)
+ *   - v' = (v * c2) + ((c3 * g) * g)
+ *   - den = (sqrt(v') / cb) + ce
+ *   - p' = p + cs * (m' / den)
+ *  TQ_OPT_RMSPROP (momentum 0, not centered):  ca = (float)alpha, c3 = (float)(1 - alpha), ce, cs = (float)(-lr)
+ *   - s' = (s * ca) + ((c3 * g) * g)
+ *   - p' = p + cs * (g / (sqrt(s') + ce))
+ *  These are the expressions of torch's single-tensor Adam and RMSprop with weight_decay 0, no amsgrad, no maximize.  They
+ *  are not bit-equal to torch, which has no single answer in bits itself (its loops are vectorised and fused differently
+ *  per backend); the lines above are the definition, torch is an accuracy reference.
+ *  Images: bf16(p') (round to nearest even) goes to the element's place in the forward image and, for conv2..conv11, in
+ *  the dgrad image; the linear layer's image gets that bf16 value as f32; biases go in as f32.  After the call the images
+ *  are bit for bit what tq_nn11_grad_load would pack from the updated masters.  No atomics; the same call gives the same
+ *  bits.
+ * Every pointer argument is a HOST array of 12 device pointers in tq_nn11_load's order and layouts.  The caller owns the
+ * state tensors as it owns the masters and the gradients (zero them before step 1); the handle keeps no optimizer state
+ * and no step count.  m_w / m_b: Adam's exp_avg, not read for TQ_OPT_RMSPROP (may be NULL); v_w / v_b: Adam's exp_avg_sq
+ * or RMSprop's square_avg.  Tensors whose pointers are all 16-byte aligned are accessed with 16-byte loads and stores.
+ * Checked before the launch (TQ_E_INVALID): a NULL handle or one that was never loaded; a kind that is neither; lr < 0,
+ * eps < 0, a beta (Adam) or alpha (RMSprop) outside [0, 1), any NaN among them; step < 1; a NULL pointer that the kind
+ * needs.  Weight decay, amsgrad, momentum, centered and maximize are outside the contract and have no argument.
+ * Precondition: the handle's images were packed from these masters, by tq_nn11_grad_load or an earlier
+ * tq_nn11_grad_opt_step.  The call allocates nothing and does not synchronise. */
+#define TQ_OPT_ADAM 0
+#define TQ_OPT_RMSPROP 1
+int tq_nn11_grad_opt_step(tq_nn11_grad* h, int kind, double lr, double beta1, double beta2, double eps, double alpha,
+                          int64_t step, float* const* weights, float* const* biases, const float* const* grad_w,
+                          const float* const* grad_b, float* const* m_w, float* const* m_b, float* const* v_w,
+                          float* const* v_b, void* stream);
 
 #ifdef __cplusplus
 }

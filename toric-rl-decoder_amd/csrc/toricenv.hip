@@ -718,3 +718,4 @@ int tq_check(tq_env* h, void* stream_) {
 #include "abi_replay.hpp"
 #include "abi_nn11.hpp"
 #include "abi_nn11_grad.hpp"
+#include "abi_nn11_opt.hpp"

@@ -12,6 +12,7 @@ hand-written HIP (csrc/nn11.hpp behind tq_nn11_*): NN11Forward wraps a model's w
   evaluate             src/evaluation.py:10-124
   NN11Forward          src/nn/torch/NN.py:10-45, src/nn/torch/util.py:21-26 (the forward as bf16 MFMA kernels)
   NN11Grad             src/Learner_mp.py:140-160 (forward, loss head and backward pass as HIP kernels)
+  NN11Optimizer        src/Learner_mp.py:81-84 (Adam / RMSprop on the masters and the re-pack, one HIP launch)
   learnerStep          src/Learner_mp.py:135-169 (one learner iteration on a device replay memory)
 """
 import ctypes as C
@@ -184,10 +185,117 @@ class NN11Grad(Handle):
         self._call(self._L.tq_nn11_grad_check)
 
 
+class NN11Optimizer:
+    """NN_11's optimizer step as one HIP launch (tq_nn11_grad_opt_step; numerics contract in include/toricenv.h): Adam or
+    RMSprop (Learner_mp.py:81-84) on the f32 masters of ``grad`` (an NN11Grad) from the ``.grad`` its backward wrote, and
+    the re-pack of the handle's bf16 images from the same registers, so no ``grad.load()`` follows (``repacks``).  In place
+    of ``torch.optim.Adam(model.parameters(), lr=...)`` / ``RMSprop``; torch's other options (weight decay, amsgrad,
+    momentum, centered, maximize) are outside the contract.  ``state_dict()`` / ``load_state_dict()`` speak
+    torch.optim's format, so the reference's checkpoints (Learner_mp.py:90) carry over in both directions."""
+
+    repacks = True
+    KINDS = {"Adam": _lib.TQ_OPT_ADAM, "RMSprop": _lib.TQ_OPT_RMSPROP}
+
+    def __init__(self, grad, kind="Adam", lr=0.00025, betas=(0.9, 0.999), eps=1e-8, alpha=0.99):
+        if kind not in self.KINDS:
+            raise ValueError(f"kind must be 'Adam' or 'RMSprop', got {kind!r}")
+        self.grad, self.kind = grad, kind
+        self._set_hyper(lr, betas, eps, alpha)
+        self.step_count = 0
+        # in model.parameters() order: conv1.weight, conv1.bias, ..., linear1.weight, linear1.bias
+        self._flat = [p for pair in grad._params for p in pair]
+        zeros = lambda: [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self._flat]
+        self._m = zeros() if kind == "Adam" else None           # exp_avg
+        self._v = zeros()                                       # exp_avg_sq / square_avg
+
+    def _set_hyper(self, lr, betas, eps, alpha):
+        lr, b1, b2, eps, alpha = float(lr), float(betas[0]), float(betas[1]), float(eps), float(alpha)
+        if not lr >= 0.0 or not eps >= 0.0:
+            raise ValueError(f"lr and eps must be >= 0, got {lr} and {eps}")
+        if self.kind == "Adam" and not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must be in [0, 1), got {(b1, b2)}")
+        if self.kind == "RMSprop" and not 0.0 <= alpha < 1.0:
+            raise ValueError(f"alpha must be in [0, 1), got {alpha}")
+        self.lr, self.betas, self.eps, self.alpha = lr, (b1, b2), eps, alpha
+
+    @staticmethod
+    def _pointers(tensors, which):
+        return None if tensors is None else (C.c_void_p * 12)(*[t.data_ptr() for t in tensors[which::2]])
+
+    def step(self):
+        """One update, number ``step_count + 1``, on the current stream: masters, state and the handle's images."""
+        for p in self._flat:
+            if p.grad is None:
+                raise ValueError("a master parameter has no .grad: call NN11Grad.backward first")
+            if p.grad.dtype != torch.float32 or not p.grad.is_contiguous() or p.grad.device != p.device:
+                raise ValueError("every .grad must be a contiguous float32 tensor on the masters' device")
+        grads = [p.grad for p in self._flat]
+        args = [self._pointers(t, k) for t in (self._flat, grads, self._m, self._v) for k in (0, 1)]
+        self.grad._call(self.grad._L.tq_nn11_grad_opt_step, self.KINDS[self.kind], self.lr, self.betas[0], self.betas[1], self.eps,
+                        self.alpha, self.step_count + 1, *args)
+        self.step_count += 1
+
+    def zero_grad(self, set_to_none=False):
+        """Nothing to do: NN11Grad.backward writes the gradients, it does not accumulate them."""
+
+    def _torch_twin(self):
+        """torch's optimizer of this kind and these hyperparameters on the same parameters (it allocates no state)"""
+        if self.kind == "Adam":
+            return torch.optim.Adam(self._flat, lr=self.lr, betas=self.betas, eps=self.eps)
+        return torch.optim.RMSprop(self._flat, lr=self.lr, alpha=self.alpha, eps=self.eps)
+
+    def state_dict(self):
+        """What torch.optim.Adam / RMSprop on ``model.parameters()`` would return after ``step_count`` steps: param_groups
+        with torch's own keys, and per parameter {'step', 'exp_avg', 'exp_avg_sq'} or {'step', 'square_avg'} (copies; no
+        state before the first step, as in torch)."""
+        sd = self._torch_twin().state_dict()
+        if self.step_count:
+            for i in range(len(self._flat)):
+                st = {"step": torch.tensor(float(self.step_count), dtype=torch.float32)}
+                if self.kind == "Adam":
+                    st["exp_avg"], st["exp_avg_sq"] = self._m[i].clone(), self._v[i].clone()
+                else:
+                    st["square_avg"] = self._v[i].clone()
+                sd["state"][i] = st
+        return sd
+
+    def load_state_dict(self, sd):
+        """Takes a torch.optim.Adam / RMSprop state_dict of NN_11's 24 parameters: the state is copied in, ``step_count``
+        and the hyperparameters are taken from it.  ValueError for an option outside the contract, for step counts that
+        differ between parameters and for wrong shapes; nothing is changed then."""
+        groups = sd["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(self._flat):
+            raise ValueError("expected one param_group with NN_11's 24 parameters")
+        g = groups[0]
+        if ("betas" in g) != (self.kind == "Adam") or ("alpha" in g) != (self.kind == "RMSprop"):
+            raise ValueError(f"the state_dict is not torch.optim.{self.kind}'s")
+        for key in ("weight_decay", "amsgrad", "maximize", "momentum", "centered"):
+            if g.get(key, 0):
+                raise ValueError(f"{key}={g[key]!r} is outside NN11Optimizer's contract")
+        state, keys = sd["state"], (("exp_avg", "exp_avg_sq") if self.kind == "Adam" else ("square_avg",))
+        if state and sorted(state.keys()) != sorted(g["params"]):
+            raise ValueError("the state must be empty or hold every parameter")
+        steps = {float(st["step"]) for st in state.values()}
+        if len(steps) > 1 or any(s < 0 or s != int(s) for s in steps):
+            raise ValueError(f"per-parameter step counts differ or are not whole numbers: {sorted(steps)}")
+        for i, pid in enumerate(g["params"] if state else ()):
+            for k in keys:
+                if k not in state[pid] or tuple(state[pid][k].shape) != tuple(self._flat[i].shape):
+                    raise ValueError(f"state of parameter {i}: {k} missing or not of shape {tuple(self._flat[i].shape)}")
+        self._set_hyper(g["lr"], g.get("betas", self.betas), g["eps"], g.get("alpha", self.alpha))
+        self.step_count = int(steps.pop()) if steps else 0
+        for i in range(len(self._flat)):
+            for k, dst in zip(keys, (self._m, self._v) if self.kind == "Adam" else (self._v,)):
+                if state:
+                    dst[i].copy_(state[g["params"][i]][k])
+                else:
+                    dst[i].zero_()
+
+
 def learnerStep(grad, target_model, memory, optimizer, batch_size, beta, discount=0.95, batch=None):
     """One iteration of Learner_mp.py:135-169 on a device PrioritizedReplayMemory: sample_batch -> learnerTargets on
     ``target_model`` (a torch module or an NN11Forward) -> ``grad.backward`` -> ``optimizer.step()`` on the masters ->
-    ``grad.load()`` -> priority_update(indices, |loss|).  ``batch``: a sample_batch result to step on instead of drawing
+    ``grad.load()`` (not after an optimizer that ``repacks``: NN11Optimizer) -> priority_update(indices, |loss|).  ``batch``: a sample_batch result to step on instead of drawing
     one (its next_state is not used).  -> (loss f32 (B,), indices i64 (B,)) device tensors."""
     if batch is None:
         batch = memory.sample_batch(batch_size, beta, next_state=False)
@@ -195,7 +303,8 @@ def learnerStep(grad, target_model, memory, optimizer, batch_size, beta, discoun
     y = learnerTargets(target_model, memory, indices, reward, terminal, discount=discount)
     loss, _ = grad.backward(state, actions, y, weights)
     optimizer.step()
-    grad.load()
+    if not getattr(optimizer, "repacks", False):
+        grad.load()
     memory.update_priorities(indices, loss.abs())
     return loss, indices
 
