@@ -21,6 +21,7 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SIZES = tuple(T.SUPPORTED_SIZES)
 CH = T.NN_11.CHANNELS
 NAMES = [f"conv{i + 1}" for i in range(11)] + ["linear1"]
+PARAMS = [f"{n}.{k}" for n in NAMES for k in ("weight", "bias")]        # the 24 tensors, in model.parameters() order
 
 
 def integer_state_dict(d):

@@ -17,9 +17,7 @@ import torch.nn.functional as F
 
 import nn11_cases as K
 
-CH = K.CH
-NAMES = K.NAMES
-PARAMS = [f"{n}.{k}" for n in NAMES for k in ("weight", "bias")]        # the 24 gradient tensors
+CH, NAMES, PARAMS = K.CH, K.NAMES, K.PARAMS                             # PARAMS: the 24 gradient tensors
 SUM_LIMIT = float(1 << 23)
 
 
@@ -279,3 +277,20 @@ def rounding_case(d):
 def mutant_grads(c, name):
     g, _ = manual_backward(c["sd"], torch.from_numpy(c["x"]), c["dq"], **MUTANTS[name])
     return g
+
+
+def play_memory(T, d, seed, device="cuda:0"):
+    """(GPU tests) a replay memory filled by epsilon = 1 play: 256 lattices, 8 steps"""
+    env = T.make("toric-code-v0", {"size": d, "min_qubit_errors": 0, "p_error": 0.1})
+    gpu = T.EnvSet(env, 256, device=device, seed=seed, numpy_io=False)
+    gpu.resetAll()
+    blk = gpu.newTransitionBlock(steps=8)
+    for t in range(8):
+        gpu.actorStep(None, block=blk, slot=t)
+    g = torch.Generator(device=device).manual_seed(seed)
+    blk.computePriorities(256, 8, torch.rand((9, 256, 3), generator=g, device=device) * 4 - 2, 0.95)
+    gpu.check()
+    gpu.close()
+    mem = T.PrioritizedReplayMemory(4096, 0.6, d=d, device=device, seed=seed)
+    mem.save_block(blk)
+    return mem

@@ -15,15 +15,13 @@ import math
 
 import numpy as np
 
+from nn11_cases import CH, NAMES, PARAMS  # noqa: F401
+
 f32 = np.float32
 HYPER = dict(lr=0.00025, betas=(0.9, 0.999), eps=1e-8, alpha=0.99)      # Learner_mp.py:81-84, torch's defaults for the rest
 STEPS = (1, 2, 1000)                                                     # bias corrections far from and near to 1
 KINDS = ("Adam", "RMSprop")
 MARGIN = 1.25                                                            # two orderings of the same few roundings
-
-CH = (2, 128, 128, 120, 111, 104, 103, 90, 80, 73, 71, 64)
-NAMES = [f"conv{i + 1}" for i in range(11)] + ["linear1"]
-PARAMS = [f"{n}.{k}" for n in NAMES for k in ("weight", "bias")]
 
 MUTANTS = {
     "m as beta1 m + c1 g": ("Adam",),

@@ -5,13 +5,11 @@ exactly once, under a header that tells whose table it is.  Exact; test-only bui
 (find_cut, the stack write's own search for two cut points where there is no table, stays a device function: the GPU tests
 of lattice ranges and of cloned offsets hold it against the same contract.)"""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_build import build_shim
 I64 = np.int64
 SENTINEL = -7
 P64 = C.POINTER(C.c_int64)
@@ -20,11 +18,7 @@ P32 = C.POINTER(C.c_int32)
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("cutshim") / "libcutshim.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_cut_points_shim.cpp"), "-o", str(out)])
-    lib = C.CDLL(str(out))
+    lib = build_shim(tmp_path_factory, "host_cut_points_shim.cpp")
     lib.shim_cut_target.restype = C.c_int64
     lib.shim_cut_target.argtypes = [C.c_int64, C.c_int64, C.c_int]
     lib.shim_cut_floor.restype = C.c_int64

@@ -89,6 +89,39 @@ def test_both_cases_are_bit_equal_to_their_references(T, handles, d, kind):
     fwd.close()
 
 
+@pytest.mark.parametrize("d", (3, 5))
+def test_a_forward_and_a_grad_handle_hold_the_same_network_after_every_load(T, d):
+    """Both handles keep their packed network in one struct with one load and one forward.  Given the same integer
+    network, and then reloaded with a second one (the conv stack of another size's integer network under the negated
+    linear layer), an NN11Forward and an NN11Grad give the same Q bits on one workgroup's perspectives and one more:
+    torch's own f32 bits, since every activation is a small integer (asserted)."""
+    n = K.group(d) + 1
+    c = GC.integer_case(d)
+    second = dict(K.integer_state_dict(d + 2))
+    second["linear1.weight"], second["linear1.bias"] = -c["sd"]["linear1.weight"], -c["sd"]["linear1.bias"]
+    x = torch.from_numpy(c["x"][:n]).to(DEV)
+    a, y = c["actions"][:n].to(DEV), c["y"][:n].to(DEV)
+    model = T.NN_11(d).to(DEV)
+    model.load_state_dict(c["sd"])
+    grad = T.NN11Grad(model, d, DEV, max_batch=n)
+    fwd = T.NN11Forward(c["sd"], d, DEV, max_rows=n)
+    seen = []
+    for sd in (c["sd"], second):
+        outs, want = K.layer_outputs(K.model_of(sd, d), torch.from_numpy(c["x"][:n]).float())
+        assert all(bool((o == o.round()).all()) and float(o.max()) < 256 for o in outs) and bool(outs[-1].any())
+        if sd is second:
+            model.load_state_dict(sd)
+            grad.load()
+            fwd.load(sd)
+        _, q = grad.backward(x, a, y)
+        assert torch.equal(q, fwd(x)) and np.array_equal(q.cpu().numpy(), want.numpy()), d
+        seen.append(want)
+    assert np.array_equal(seen[0].numpy(), c["q"][:n]) and not torch.equal(seen[0], seen[1])
+    grad.check()
+    grad.close()
+    fwd.close()
+
+
 @pytest.mark.parametrize("d", (7, 17))
 def test_a_step_after_a_larger_one_gives_the_bits_of_a_fresh_handle(T, d):
     c = GC.rounding_case(d)
@@ -162,23 +195,6 @@ def test_arguments_are_checked_before_any_launch(T):
     g.close()
 
 
-def play_memory(T, d, seed):
-    """a replay memory filled by epsilon = 1 play: 256 lattices, 8 steps"""
-    env = T.make("toric-code-v0", {"size": d, "min_qubit_errors": 0, "p_error": 0.1})
-    gpu = T.EnvSet(env, 256, device=DEV, seed=seed, numpy_io=False)
-    gpu.resetAll()
-    blk = gpu.newTransitionBlock(steps=8)
-    for t in range(8):
-        gpu.actorStep(None, block=blk, slot=t)
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    blk.computePriorities(256, 8, torch.rand((9, 256, 3), generator=g, device=DEV) * 4 - 2, 0.95)
-    gpu.check()
-    gpu.close()
-    mem = T.PrioritizedReplayMemory(4096, 0.6, d=d, device=DEV, seed=seed)
-    mem.save_block(blk)
-    return mem
-
-
 def rel_l2(a, b):
     return float(torch.linalg.norm((a.double() - b.double()).flatten()) / torch.linalg.norm(b.double().flatten()))
 
@@ -196,7 +212,7 @@ def test_trained_weights_stay_within_the_contracts_own_error(T, d):
     B = 64
     sd = K.trained_state_dict(d)
     model = K.model_of(sd, d).to(DEV)
-    mem = play_memory(T, d, 40 + d)
+    mem = GC.play_memory(T, d, 40 + d)
     batches = []
     for _ in range(5):
         state, actions, reward, _, terminal, weights, indices = mem.sample_batch(B, 0.4, next_state=False)
@@ -235,7 +251,7 @@ def test_trained_weights_stay_within_the_contracts_own_error(T, d):
 
 def test_twenty_learner_steps_on_one_sample_lower_the_loss_and_write_the_priorities(T):
     d, B, beta, alpha, steps, lr = 5, 64, 0.4, 0.6, 20, 1e-4      # 1e-3 diverges in f32 torch as well: y is near 100
-    mem = play_memory(T, d, 77)
+    mem = GC.play_memory(T, d, 77)
     target = T.NN11Forward(K.trained_state_dict(d), d, DEV, max_rows=4096)
     torch.manual_seed(5)
     model = T.NN_11(d).to(DEV)

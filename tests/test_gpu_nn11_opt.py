@@ -28,23 +28,6 @@ def T():
     return T
 
 
-def play_memory(T, d, seed):
-    """a replay memory filled by epsilon = 1 play: 256 lattices, 8 steps (as tests/test_gpu_nn11_grad.py fills its own)"""
-    env = T.make("toric-code-v0", {"size": d, "min_qubit_errors": 0, "p_error": 0.1})
-    gpu = T.EnvSet(env, 256, device=DEV, seed=seed, numpy_io=False)
-    gpu.resetAll()
-    blk = gpu.newTransitionBlock(steps=8)
-    for t in range(8):
-        gpu.actorStep(None, block=blk, slot=t)
-    g = torch.Generator(device=DEV).manual_seed(seed)
-    blk.computePriorities(256, 8, torch.rand((9, 256, 3), generator=g, device=DEV) * 4 - 2, 0.95)
-    gpu.check()
-    gpu.close()
-    mem = T.PrioritizedReplayMemory(4096, 0.6, d=d, device=DEV, seed=seed)
-    mem.save_block(blk)
-    return mem
-
-
 def state_of(opt, i):
     """(m, v) of parameter i as numpy; m None for RMSprop"""
     return (None if opt._m is None else opt._m[i].cpu().numpy()), opt._v[i].cpu().numpy()
@@ -262,7 +245,7 @@ def test_twenty_learner_steps_without_a_load(T):
     and twin handle, on one fixed sample: finite losses, a clean latch, and if torch's loss fell the device's did too.
     The trajectories are printed (profiles/nn11_opt_accuracy.txt holds them); no number is put on their distance."""
     d, B, beta, steps = 5, 64, 0.4, 20
-    mem = play_memory(T, d, 78)
+    mem = GC.play_memory(T, d, 78)
     target = T.NN11Forward(K.trained_state_dict(d), d, DEV, max_rows=4096)
     torch.manual_seed(6)
     model = T.NN_11(d).to(DEV)

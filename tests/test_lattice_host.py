@@ -3,25 +3,19 @@ tests/host_lattice_shim.cpp instantiates the same templates the HIP kernels use,
 into a temp dir, and every operation is compared with the oracle.  Test-only build: the product
 itself has no CPU path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from oracle import toric_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_build import build_shim
 SIZES = (3, 5, 7, 9, 11, 13, 15, 17, 19, 21)
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("shim") / "libshim.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_lattice_shim.cpp"), "-o", str(out)])
-    return C.CDLL(str(out))
+    return build_shim(tmp_path_factory, "host_lattice_shim.cpp")
 
 
 def P(a):

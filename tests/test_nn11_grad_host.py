@@ -3,8 +3,6 @@ forward and dgrad pack routines, the index functions, the four tap -> source pix
 through tests/host_nn11_grad_shim.cpp and driven by a scalar forward + backward under the numerics contract of
 include/toricenv.h, against the two cases of tests/nn11_grad_cases.py.  Test-only build: the product has no CPU path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,18 +12,14 @@ import toric_rl_decoder_amd as T
 
 import nn11_cases as K
 import nn11_grad_cases as GC
+from host_build import build_shim
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FULL = 3                                                   # NN11_FULL of csrc/nn11.hpp
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("nn11gradshim") / "libnn11gradshim.so"
-    subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_nn11_grad_shim.cpp"), "-o", str(out)])
-    lib = C.CDLL(str(out))
+    lib = build_shim(tmp_path_factory, "host_nn11_grad_shim.cpp", fast=True, openmp=True)
     vp = C.c_void_p
     lib.shim_nn11_grad.restype = C.c_int
     lib.shim_nn11_grad.argtypes = [C.c_int, C.POINTER(vp), C.POINTER(vp), vp, C.c_int, vp, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp)]

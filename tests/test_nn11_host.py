@@ -3,8 +3,6 @@ functions of the weight / activation / linear images and the tap -> source pixel
 with g++ through tests/host_nn11_shim.cpp and driven by a scalar forward under the numerics contract of
 include/toricenv.h.  Test-only build: the product itself has no CPU path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,17 +11,12 @@ import torch
 import toric_rl_decoder_amd as T
 
 import nn11_cases as K
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_build import build_shim
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("nn11shim") / "libnn11shim.so"
-    subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", "-ffp-contract=off", "-fopenmp", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_nn11_shim.cpp"), "-o", str(out)])
-    lib = C.CDLL(str(out))
+    lib = build_shim(tmp_path_factory, "host_nn11_shim.cpp", fast=True, openmp=True)
     lib.shim_nn11_forward.restype = C.c_int
     lib.shim_nn11_forward.argtypes = [C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_int64,
                                       C.c_void_p]

@@ -5,8 +5,6 @@ the torch.optim side of policy.NN11Optimizer (state_dict both ways) on CPU tenso
 CPU path."""
 import copy
 import ctypes as C
-import os
-import subprocess
 import types
 
 import numpy as np
@@ -16,8 +14,7 @@ import torch
 import toric_rl_decoder_amd as T
 
 import nn11_opt_cases as OC
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_build import build_shim
 KIND_ID = {"Adam": 0, "RMSprop": 1}
 H = OC.HYPER
 HYPER_ARGS = (H["lr"], H["betas"][0], H["betas"][1], H["eps"], H["alpha"])
@@ -25,11 +22,7 @@ HYPER_ARGS = (H["lr"], H["betas"][0], H["betas"][1], H["eps"], H["alpha"])
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("nn11optshim") / "libnn11optshim.so"
-    subprocess.check_call(["g++", "-O3", "-march=native", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_nn11_opt_shim.cpp"), "-o", str(out)])
-    lib = C.CDLL(str(out))
+    lib = build_shim(tmp_path_factory, "host_nn11_opt_shim.cpp", fast=True)
     vp, d = C.c_void_p, C.c_double
     hyper = [C.c_int, d, d, d, d, d, C.c_int64]
     lib.shim_nn11_opt_consts.restype = None

@@ -5,7 +5,6 @@ exactly.  Test-only build: the product itself has no CPU path."""
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,17 +12,13 @@ import pytest
 import toric_rl_decoder_amd as T
 from oracle import toric_oracle as O
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_build import ROOT, build_shim
 F32 = np.float32
 
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("tdshim") / "libtdshim.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_td_target_shim.cpp"), "-o", str(out)])
-    lib = C.CDLL(str(out))
+    lib = build_shim(tmp_path_factory, "host_td_target_shim.cpp")
     lib.shim_td_target.restype = None
     lib.shim_td_target.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
                                    C.c_float, C.c_void_p]

@@ -4,13 +4,11 @@ contract stated here in numpy: the workgroups' stack and positions intervals til
 a range's origin is the line that holds its first element, need_extra is the fewest perspectives that fill its last
 lines, and the slots' fine parts tile the table.  Exact; test-only build: the product itself has no CPU path."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from host_build import build_shim
 I64 = np.int64
 WGS = 8
 P_ALL = (0, 1, 2, 3, 10, 11, 43, 1000, 100003)
@@ -19,11 +17,7 @@ FIELDS = ("org", "head", "a0", "a1", "porg", "phead", "pa0", "pa1", "need_extra"
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("rangeshim") / "librangeshim.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_stream_range_shim.cpp"), "-o", str(out)])
-    lib = C.CDLL(str(out))
+    lib = build_shim(tmp_path_factory, "host_stream_range_shim.cpp")
     lib.shim_stream_range.restype = None
     lib.shim_stream_range.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p]
     lib.shim_slot_fine_parts.restype = None

@@ -4,7 +4,6 @@ the chunks an ingest rebuilds, and the sampler -- the draws of k_replay_sample w
 the reference's sample loop pick for pick.  Exact; test-only build: the product itself has no CPU path."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,8 +11,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import replay_oracle as RO  # noqa: E402
+from host_build import build_shim  # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I64 = C.c_int64
 P64 = C.POINTER(C.c_int64)
 PF64 = C.POINTER(C.c_double)
@@ -23,11 +22,7 @@ STAGE_LEVELS, SEG, CHUNK_LG = 13, 6, 11          # RP_STAGE_LEVELS, RP_SEG, RP_C
 
 @pytest.fixture(scope="module")
 def shim(tmp_path_factory):
-    out = tmp_path_factory.mktemp("sumtreeshim") / "libsumtreeshim.so"
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
-                           "-I", os.path.join(ROOT, "toric-rl-decoder_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "host_sum_tree_shim.cpp"), "-o", str(out)])
-    lib = C.CDLL(str(out))
+    lib = build_shim(tmp_path_factory, "host_sum_tree_shim.cpp")
     for name, res, args in (
             ("tree_levels", C.c_int, [I64]), ("tree_nodes", I64, [C.c_int]), ("level_first", I64, [C.c_int]),
             ("left_child", I64, [I64]), ("leaf_node", I64, [C.c_int, I64]), ("leaf_of_node", I64, [C.c_int, I64]),

@@ -1,68 +1,102 @@
-// The NN_11 forward's entry points of include/toricenv.h (part of toricenv.hip's translation unit).
+// The NN_11 forward's entry points of include/toricenv.h (part of toricenv.hip's translation unit), and what they share
+// with the learner step's (abi_nn11_grad.hpp): the packed network on the device, the one launcher of k_nn11_conv and
+// the forward over it.
 #pragma once
 #include <new>
 
 #include "abi_util.hpp"
-#include "nn11.hpp"
+#include "nn11_grad.hpp"
 
-struct tq_nn11 {                           // made by `new tq_nn11()`: every member starts as zero
-    int d, device, loaded;
-    int64_t max_rows;
+namespace {
+// The packed network of one handle.  The padding of every image is the zeros alloc() leaves: k_nn11_pack writes it as
+// zeros again, and the optimizer's re-pack (k_nn11_opt) does not touch it.
+struct NN11Net {
+    int loaded;
     uint16_t* wimg;                        // the eleven conv layers' bf16 fragment images, back to back
     float* bias;                           // their padded f32 biases, back to back
     float* limg;                           // linear weights f32[3][(d-2)^2][64] (bf16-rounded values)
     float* lbias;                          // f32[3]
-    uint16_t* act[2];                      // activation images of one pass, taking turns: max_rows * d^2 * 128 bf16 each
-    DeviceBuffers mem;
+    uint16_t* dimg;                        // the dgrad fragment images of conv2..conv11, back to back; NULL: forward only
+
+    void alloc(DeviceBuffers& mem, int d, bool with_dgrad) {
+        constexpr int L = tq::NN11_LAYERS;
+        mem.zeroed(&wimg, (size_t)tq::nn11_wimg_offset(L + 1) * sizeof(uint16_t));
+        mem.zeroed(&bias, (size_t)tq::nn11_bias_offset(L + 1) * sizeof(float));
+        mem.zeroed(&limg, (size_t)tq::nn11_lin_elems(d) * sizeof(float));
+        mem.zeroed(&lbias, 16);
+        if (with_dgrad) mem.zeroed(&dimg, (size_t)tq::nn11_dimg_offset(L + 1) * sizeof(uint16_t));
+    }
+    // torch-layout f32 weights and biases (12 device pointers each) -> the images, on `stream`
+    int load(int d, const float* const* weights, const float* const* biases, hipStream_t stream) {
+        constexpr int L = tq::NN11_LAYERS;
+        if (!weights || !biases) return fail(TQ_E_INVALID, "weights / biases is NULL");
+        tq::NN11Pack p;
+        for (int i = 0; i <= L; ++i) {
+            if (!weights[i] || !biases[i]) return fail(TQ_E_INVALID, "weights[%d] / biases[%d] is NULL", i, i);
+            p.w[i] = weights[i]; p.b[i] = biases[i];
+        }
+        if (int rc = launch(tq::k_nn11_pack, dim3(64, L + 1), dim3(256), stream, p, d, wimg, bias, limg, lbias)) return rc;
+        if (dimg)
+            if (int rc = launch(tq::k_nn11_pack_dgrad, dim3(64, L - 1), dim3(256), stream, p, dimg)) return rc;
+        loaded = 1;
+        return TQ_OK;
+    }
 };
 
-namespace {
-#define NHANDLE(h)                                                \
-    DeviceGuard _guard;                                           \
-    if (!(h)) return fail(TQ_E_INVALID, "NULL nn11 handle");      \
-    if (int _rc = _guard.enter_device((h)->device)) return _rc;   \
-    hipStream_t stream = (hipStream_t)stream_
-
-template <int D, int KS, int NT, int MODE>
-int nn11_conv(const tq_nn11* h, int l, const void* in, int dtype, uint16_t* out, int64_t rows, hipStream_t stream) {
+// One convolution over `rows` perspectives.  Every k_nn11_conv the library holds is in the list below, by (k-steps,
+// n-tiles, mode): five shapes of the forward (EPI = NN11_EPI_BIAS_RELU, `aux` the padded bias) and four of the dgrad
+// (NN11_EPI_MASK, `aux` the activation image whose sign masks).
+template <int D, int EPI>
+int nn11_conv(int mode, int ks, int nt, const void* in, int dtype, const uint16_t* img, const void* aux, uint16_t* out, int64_t rows,
+              hipStream_t stream) {
     constexpr int G = tq::NN11Geom<D>::G, THREADS = tq::NN11Geom<D>::THREADS;
-    return launch(tq::k_nn11_conv<D, KS, NT, MODE>, dim3((unsigned)((rows + G - 1) / G)), dim3(THREADS), stream, in, dtype,
-                  h->wimg + tq::nn11_wimg_offset(l), h->bias + tq::nn11_bias_offset(l), out, rows);
+    const dim3 grid((unsigned)((rows + G - 1) / G)), block(THREADS);
+#define NN11_SHAPE(KS, NT, MODE)                         \
+    if (ks == KS && nt == NT && mode == tq::MODE)        \
+        return launch(tq::k_nn11_conv<D, KS, NT, tq::MODE, EPI>, grid, block, stream, in, dtype, img, aux, out, rows)
+    if constexpr (EPI == tq::NN11_EPI_BIAS_RELU) {
+        NN11_SHAPE(2, 4, NN11_CIRCULAR);
+        NN11_SHAPE(6, 2, NN11_VALID);
+        NN11_SHAPE(8, 4, NN11_ZERO);
+        NN11_SHAPE(8, 3, NN11_ZERO);
+        NN11_SHAPE(6, 3, NN11_ZERO);
+    } else {
+        NN11_SHAPE(4, 3, NN11_FULL);
+        NN11_SHAPE(8, 4, NN11_ZERO);
+        NN11_SHAPE(6, 4, NN11_ZERO);
+        NN11_SHAPE(6, 3, NN11_ZERO);
+    }
+#undef NN11_SHAPE
+    return fail(TQ_E_INVALID, "nn11: no kernel for layer shape (%d k-steps, %d n-tiles, mode %d, epilogue %d)", ks, nt, mode, EPI);
 }
 
-// one pass of at most max_rows perspectives: conv1 from the stack, conv2..11 between the two images, the linear layer
+// The forward of `rows` perspectives: conv l = 1..11 writes its bf16 image to out[l] (conv1 reads the stack, conv l
+// reads out[l - 1]), the linear layer reads out[11] and writes q.
 template <int D>
-int nn11_pass(const tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, hipStream_t stream) {
-    uint16_t* a = h->act[0];
-    uint16_t* b = h->act[1];
-    if (int rc = nn11_conv<D, 2, 4, tq::NN11_CIRCULAR>(h, 1, stack, dtype, a, rows, stream)) return rc;
-    for (int l = 2; l <= tq::NN11_LAYERS; ++l) {
-        const int ks = tq::nn11_ksteps(l), nt = tq::nn11_ntiles(l);
-        int rc;
-        if (l == tq::NN11_LAYERS) rc = nn11_conv<D, 6, 2, tq::NN11_VALID>(h, l, a, 0, b, rows, stream);
-        else if (ks == 8 && nt == 4) rc = nn11_conv<D, 8, 4, tq::NN11_ZERO>(h, l, a, 0, b, rows, stream);
-        else if (ks == 8 && nt == 3) rc = nn11_conv<D, 8, 3, tq::NN11_ZERO>(h, l, a, 0, b, rows, stream);
-        else if (ks == 6 && nt == 3) rc = nn11_conv<D, 6, 3, tq::NN11_ZERO>(h, l, a, 0, b, rows, stream);
-        else rc = fail(TQ_E_INVALID, "nn11: no kernel for layer %d (%d k-steps, %d n-tiles)", l, ks, nt);
-        if (rc) return rc;
-        uint16_t* t = a; a = b; b = t;
-    }
-    return launch(tq::k_nn11_linear, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, a, h->limg, h->lbias, q, rows,
+int nn11_forward(const NN11Net& net, const void* stack, int dtype, int64_t rows, uint16_t* const* out, float* q, hipStream_t stream) {
+    constexpr int L = tq::NN11_LAYERS;
+    for (int l = 1; l <= L; ++l)
+        if (int rc = nn11_conv<D, tq::NN11_EPI_BIAS_RELU>(tq::nn11_mode(l), tq::nn11_ksteps(l), tq::nn11_ntiles(l),
+                                                          l == 1 ? stack : out[l - 1], l == 1 ? dtype : 0,
+                                                          net.wimg + tq::nn11_wimg_offset(l), net.bias + tq::nn11_bias_offset(l),
+                                                          out[l], rows, stream)) return rc;
+    return launch(tq::k_nn11_linear, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, out[L], net.limg, net.lbias, q, rows,
                   tq::nn11_out_pixels(D));
 }
 }  // namespace
 
+struct tq_nn11 {                           // made by `new tq_nn11()`: every member starts as zero
+    int d, device;
+    int64_t max_rows;
+    NN11Net net;
+    uint16_t* act[2];                      // activation images of one pass, taking turns: max_rows * d^2 * 128 bf16 each
+    uint16_t* out[tq::NN11_LAYERS + 1];    // out[l], l = 1..11: the one of the two that layer l writes
+    DeviceBuffers mem;
+};
+
 extern "C" {
 
-int tq_nn11_destroy(tq_nn11* h) {
-    if (!h) return TQ_OK;
-    DeviceGuard guard;
-    (void)guard.enter_device(h->device);
-    h->mem.release_all();
-    (void)hipGetLastError();
-    delete h;
-    return TQ_OK;
-}
+int tq_nn11_destroy(tq_nn11* h) { return destroy_handle(h); }
 
 int tq_nn11_create(tq_nn11** out, int d, int64_t max_rows, int device) {
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
@@ -75,12 +109,10 @@ int tq_nn11_create(tq_nn11** out, int d, int64_t max_rows, int device) {
     tq_nn11* h = new (std::nothrow) tq_nn11();
     if (!h) return fail(TQ_E_INVALID, "out of host memory");
     h->d = d; h->device = device; h->max_rows = max_rows;
-    h->mem.zeroed(&h->wimg, (size_t)tq::nn11_wimg_offset(tq::NN11_LAYERS + 1) * sizeof(uint16_t));
-    h->mem.zeroed(&h->bias, (size_t)tq::nn11_bias_offset(tq::NN11_LAYERS + 1) * sizeof(float));
-    h->mem.zeroed(&h->limg, (size_t)tq::nn11_lin_elems(d) * sizeof(float));
-    h->mem.zeroed(&h->lbias, 16);
+    h->net.alloc(h->mem, d, false);
     for (int i = 0; i < 2; ++i)
         h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::NN11_MAX_CP * sizeof(uint16_t));
+    for (int l = 1; l <= tq::NN11_LAYERS; ++l) h->out[l] = h->act[(l + 1) & 1];
     hipError_t e = h->mem.err;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) { tq_nn11_destroy(h); return fail(TQ_E_HIP, "nn11 allocation failed: %s", hipGetErrorString(e)); }
@@ -89,22 +121,13 @@ int tq_nn11_create(tq_nn11** out, int d, int64_t max_rows, int device) {
 }
 
 int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* biases, void* stream_) {
-    NHANDLE(h);
-    if (!weights || !biases) return fail(TQ_E_INVALID, "weights / biases is NULL");
-    tq::NN11Pack p;
-    for (int i = 0; i <= tq::NN11_LAYERS; ++i) {
-        if (!weights[i] || !biases[i]) return fail(TQ_E_INVALID, "weights[%d] / biases[%d] is NULL", i, i);
-        p.w[i] = weights[i]; p.b[i] = biases[i];
-    }
-    if (int rc = launch(tq::k_nn11_pack, dim3(64, tq::NN11_LAYERS + 1), dim3(256), stream, p, h->d, h->wimg, h->bias, h->limg,
-                        h->lbias)) return rc;
-    h->loaded = 1;
-    return TQ_OK;
+    ENTER(h, "nn11 handle");
+    return h->net.load(h->d, weights, biases, stream);
 }
 
 int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream_) {
-    NHANDLE(h);
-    if (!h->loaded) return fail(TQ_E_INVALID, "nn11 forward before tq_nn11_load");
+    ENTER(h, "nn11 handle");
+    if (!h->net.loaded) return fail(TQ_E_INVALID, "nn11 forward before tq_nn11_load");
     if (dtype < TQ_F32 || dtype > TQ_U8) return fail(TQ_E_INVALID, "bad stack dtype %d", dtype);
     if (rows < 0) return fail(TQ_E_INVALID, "negative rows");
     if (rows == 0) return TQ_OK;
@@ -113,11 +136,11 @@ int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, floa
     REQUIRE_ALIGNED16(q, "q");
     const int64_t esize = dtype == TQ_F32 ? 4 : (dtype == TQ_U8 ? 1 : 2);
     const int64_t row_bytes = 2 * (int64_t)h->d * h->d * esize;
-    return by_size(h->d, [&](auto D) {
+    return by_size(h->d, [&](auto D) {                     // passes of at most max_rows perspectives
         for (int64_t first = 0; first < rows; first += h->max_rows) {
             const int64_t n = rows - first < h->max_rows ? rows - first : h->max_rows;
-            if (int rc = nn11_pass<D()>(h, static_cast<const char*>(stack) + first * row_bytes, dtype, n,
-                                        q + first * tq::NN11_OUT, stream)) return rc;
+            if (int rc = nn11_forward<D()>(h->net, static_cast<const char*>(stack) + first * row_bytes, dtype, n, h->out,
+                                           q + first * tq::NN11_OUT, stream)) return rc;
         }
         return (int)TQ_OK;
     });

@@ -2,16 +2,11 @@
 #pragma once
 #include <new>
 
-#include "abi_util.hpp"
-#include "nn11_grad.hpp"
+#include "abi_nn11.hpp"
 
 struct tq_nn11_grad {                      // made by `new tq_nn11_grad()`: every member starts as zero
-    int d, device, loaded, max_batch;
-    uint16_t* wimg;                        // as tq_nn11: forward fragment images, padded biases, linear image and bias
-    float* bias;
-    float* limg;
-    float* lbias;
-    uint16_t* dimg;                        // the dgrad fragment images of conv2..conv11, back to back
+    int d, device, max_batch;
+    NN11Net net;                           // as tq_nn11's, with the dgrad images
     uint16_t* act[tq::NN11_LAYERS + 1];    // act[l], l = 1..11: layer l's bf16 output, max_batch * pixels(l) * cpad(cout(l))
     uint16_t* g[2];                        // gradient images taking turns: max_batch * d^2 * 128 bf16 each
     float* q;                              // f32[max_batch][3], used when the caller passes no q
@@ -24,53 +19,12 @@ struct tq_nn11_grad {                      // made by `new tq_nn11_grad()`: ever
 };
 
 namespace {
-#define GHANDLE(h)                                                  \
-    DeviceGuard _guard;                                             \
-    if (!(h)) return fail(TQ_E_INVALID, "NULL nn11 grad handle");   \
-    if (int _rc = _guard.enter_device((h)->device)) return _rc;     \
-    hipStream_t stream = (hipStream_t)stream_
-
-template <int D, int KS, int NT, int MODE, int EPI>
-int nn11g_conv(const void* in, int dtype, const uint16_t* img, const void* aux, uint16_t* out, int64_t rows, hipStream_t stream) {
-    constexpr int G = tq::NN11Geom<D>::G, THREADS = tq::NN11Geom<D>::THREADS;
-    return launch(tq::k_nn11_conv<D, KS, NT, MODE, EPI>, dim3((unsigned)((rows + G - 1) / G)), dim3(THREADS), stream, in, dtype,
-                  img, aux, out, rows);
-}
-
-// the forward of abi_nn11.hpp's nn11_pass with every layer's output kept
-template <int D>
-int nn11g_forward(const tq_nn11_grad* h, const void* stack, int dtype, int64_t n, float* q, hipStream_t stream) {
-    constexpr int F = tq::NN11_EPI_BIAS_RELU;
-    for (int l = 1; l <= tq::NN11_LAYERS; ++l) {
-        const int ks = tq::nn11_ksteps(l), nt = tq::nn11_ntiles(l);
-        const uint16_t* img = h->wimg + tq::nn11_wimg_offset(l);
-        const float* b = h->bias + tq::nn11_bias_offset(l);
-        const uint16_t* in = h->act[l - 1];
-        int rc;
-        if (l == 1) rc = nn11g_conv<D, 2, 4, tq::NN11_CIRCULAR, F>(stack, dtype, img, b, h->act[1], n, stream);
-        else if (l == tq::NN11_LAYERS) rc = nn11g_conv<D, 6, 2, tq::NN11_VALID, F>(in, 0, img, b, h->act[l], n, stream);
-        else if (ks == 8 && nt == 4) rc = nn11g_conv<D, 8, 4, tq::NN11_ZERO, F>(in, 0, img, b, h->act[l], n, stream);
-        else if (ks == 8 && nt == 3) rc = nn11g_conv<D, 8, 3, tq::NN11_ZERO, F>(in, 0, img, b, h->act[l], n, stream);
-        else if (ks == 6 && nt == 3) rc = nn11g_conv<D, 6, 3, tq::NN11_ZERO, F>(in, 0, img, b, h->act[l], n, stream);
-        else rc = fail(TQ_E_INVALID, "nn11 grad: no forward kernel for layer %d (%d k-steps, %d n-tiles)", l, ks, nt);
-        if (rc) return rc;
-    }
-    return launch(tq::k_nn11_linear, dim3((unsigned)((n + 3) / 4)), dim3(256), stream, h->act[tq::NN11_LAYERS], h->limg, h->lbias,
-                  q, n, tq::nn11_out_pixels(D));
-}
-
-// G_l (in `g`) -> the gradient of layer l - 1's pre-activation (in `out`), l = 2..11
+// G_l (in `g`) -> the gradient of layer l - 1's pre-activation (in `out`), l = 2..11: the convolution over layer l's dgrad
+// image, masked by the sign of act[l - 1]
 template <int D>
 int nn11g_dgrad(const tq_nn11_grad* h, int l, const uint16_t* g, uint16_t* out, int64_t n, hipStream_t stream) {
-    constexpr int M = tq::NN11_EPI_MASK;
-    const int ks = tq::nn11_dksteps(l), nt = tq::nn11_dntiles(l);
-    const uint16_t* img = h->dimg + tq::nn11_dimg_offset(l);
-    const uint16_t* mask = h->act[l - 1];
-    if (l == tq::NN11_LAYERS) return nn11g_conv<D, 4, 3, tq::NN11_FULL, M>(g, 0, img, mask, out, n, stream);
-    if (ks == 8 && nt == 4) return nn11g_conv<D, 8, 4, tq::NN11_ZERO, M>(g, 0, img, mask, out, n, stream);
-    if (ks == 6 && nt == 4) return nn11g_conv<D, 6, 4, tq::NN11_ZERO, M>(g, 0, img, mask, out, n, stream);
-    if (ks == 6 && nt == 3) return nn11g_conv<D, 6, 3, tq::NN11_ZERO, M>(g, 0, img, mask, out, n, stream);
-    return fail(TQ_E_INVALID, "nn11 grad: no dgrad kernel for layer %d (%d k-steps, %d n-tiles)", l, ks, nt);
+    return nn11_conv<D, tq::NN11_EPI_MASK>(l == tq::NN11_LAYERS ? tq::NN11_FULL : tq::NN11_ZERO, tq::nn11_dksteps(l), tq::nn11_dntiles(l),
+                                           g, 0, h->net.dimg + tq::nn11_dimg_offset(l), h->act[l - 1], out, n, stream);
 }
 
 // dW_l and db_l from G_l (in `g`) and layer l's input, l = 1..11
@@ -97,12 +51,12 @@ template <int D>
 int nn11g_step(const tq_nn11_grad* h, const void* state, int dtype, int n, const int64_t* actions, const float* y, const float* w,
                float* q, float* loss, float* const* gw, float* const* gb, hipStream_t stream) {
     constexpr int L = tq::NN11_LAYERS, NPIX = tq::NN11Geom<D>::OPIX, F = NPIX * 64;
-    if (int rc = nn11g_forward<D>(h, state, dtype, n, q, stream)) return rc;
+    if (int rc = nn11_forward<D>(h->net, state, dtype, n, h->act, q, stream)) return rc;      // every layer's output kept
     if (int rc = launch_1d(tq::k_nn11_head, n, stream, q, actions, y, w, n, loss, h->dq, h->latch)) return rc;
     if (int rc = launch(tq::k_nn11_dblin, dim3(1), dim3(256), stream, h->dq, n, gb[L])) return rc;
     uint16_t* g = h->g[0];
     uint16_t* o = h->g[1];
-    if (int rc = launch_1d(tq::k_nn11_g11, (int64_t)n * F, stream, h->dq, h->limg, h->act[L], g, n, NPIX)) return rc;
+    if (int rc = launch_1d(tq::k_nn11_g11, (int64_t)n * F, stream, h->dq, h->net.limg, h->act[L], g, n, NPIX)) return rc;
     const int slices = (n + tq::NN11_LIN_SLICE - 1) / tq::NN11_LIN_SLICE;
     if (int rc = launch(tq::k_nn11_lin_part, dim3((F + 255) / 256, slices), dim3(256), stream, h->dq, h->act[L], h->lpart, n, NPIX)) return rc;
     if (int rc = launch_1d(tq::k_nn11_lin_reduce, (int64_t)tq::NN11_OUT * F, stream, h->lpart, slices, NPIX, gw[L])) return rc;
@@ -118,15 +72,7 @@ int nn11g_step(const tq_nn11_grad* h, const void* state, int dtype, int n, const
 
 extern "C" {
 
-int tq_nn11_grad_destroy(tq_nn11_grad* h) {
-    if (!h) return TQ_OK;
-    DeviceGuard guard;
-    (void)guard.enter_device(h->device);
-    h->mem.release_all();
-    (void)hipGetLastError();
-    delete h;
-    return TQ_OK;
-}
+int tq_nn11_grad_destroy(tq_nn11_grad* h) { return destroy_handle(h); }
 
 int tq_nn11_grad_create(tq_nn11_grad** out, int d, int max_batch, int device) {
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
@@ -141,11 +87,7 @@ int tq_nn11_grad_create(tq_nn11_grad** out, int d, int max_batch, int device) {
     h->d = d; h->device = device; h->max_batch = max_batch;
     constexpr int L = tq::NN11_LAYERS;
     const size_t n = (size_t)max_batch;
-    h->mem.zeroed(&h->wimg, (size_t)tq::nn11_wimg_offset(L + 1) * sizeof(uint16_t));
-    h->mem.zeroed(&h->bias, (size_t)tq::nn11_bias_offset(L + 1) * sizeof(float));
-    h->mem.zeroed(&h->limg, (size_t)tq::nn11_lin_elems(d) * sizeof(float));
-    h->mem.zeroed(&h->lbias, 16);
-    h->mem.zeroed(&h->dimg, (size_t)tq::nn11_dimg_offset(L + 1) * sizeof(uint16_t));
+    h->net.alloc(h->mem, d, true);
     for (int l = 1; l <= L; ++l)
         h->mem.zeroed(&h->act[l], n * tq::nn11_layer_pixels(l, d) * tq::nn11_cpad(tq::nn11_cout(l)) * sizeof(uint16_t));
     for (int i = 0; i < 2; ++i) h->mem.zeroed(&h->g[i], n * d * d * tq::NN11_MAX_CP * sizeof(uint16_t));
@@ -165,24 +107,14 @@ int tq_nn11_grad_create(tq_nn11_grad** out, int d, int max_batch, int device) {
 }
 
 int tq_nn11_grad_load(tq_nn11_grad* h, const float* const* weights, const float* const* biases, void* stream_) {
-    GHANDLE(h);
-    if (!weights || !biases) return fail(TQ_E_INVALID, "weights / biases is NULL");
-    tq::NN11Pack p;
-    for (int i = 0; i <= tq::NN11_LAYERS; ++i) {
-        if (!weights[i] || !biases[i]) return fail(TQ_E_INVALID, "weights[%d] / biases[%d] is NULL", i, i);
-        p.w[i] = weights[i]; p.b[i] = biases[i];
-    }
-    if (int rc = launch(tq::k_nn11_pack, dim3(64, tq::NN11_LAYERS + 1), dim3(256), stream, p, h->d, h->wimg, h->bias, h->limg,
-                        h->lbias)) return rc;
-    if (int rc = launch(tq::k_nn11_pack_dgrad, dim3(64, tq::NN11_LAYERS - 1), dim3(256), stream, p, h->dimg)) return rc;
-    h->loaded = 1;
-    return TQ_OK;
+    ENTER(h, "nn11 grad handle");
+    return h->net.load(h->d, weights, biases, stream);
 }
 
 int tq_nn11_grad_step(tq_nn11_grad* h, const void* state, int dtype, int n, const int64_t* actions_idx, const float* y, const float* w,
                       float* q, float* loss, float* const* grad_w, float* const* grad_b, void* stream_) {
-    GHANDLE(h);
-    if (!h->loaded) return fail(TQ_E_INVALID, "nn11 grad step before tq_nn11_grad_load");
+    ENTER(h, "nn11 grad handle");
+    if (!h->net.loaded) return fail(TQ_E_INVALID, "nn11 grad step before tq_nn11_grad_load");
     if (dtype < TQ_F32 || dtype > TQ_U8) return fail(TQ_E_INVALID, "bad state dtype %d", dtype);
     if (n <= 0 || n > h->max_batch) return fail(TQ_E_INVALID, "n must be in 1..max_batch = %d (got %d)", h->max_batch, n);
     if (!state || !actions_idx || !y || !loss) return fail(TQ_E_INVALID, "state / actions_idx / y / loss is NULL");
@@ -196,7 +128,7 @@ int tq_nn11_grad_step(tq_nn11_grad* h, const void* state, int dtype, int n, cons
 }
 
 int tq_nn11_grad_check(tq_nn11_grad* h, void* stream_) {
-    GHANDLE(h);
+    ENTER(h, "nn11 grad handle");
     int flag = 0;
     if (int rc = read_latch(h->latch, stream, &flag)) return rc;
     if (flag & tq::NN11_ERR_ACTION) return fail(TQ_E_ACTION, "nn11 grad step: an actions_idx outside 0..2 was given");

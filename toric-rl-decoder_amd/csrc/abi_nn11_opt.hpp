@@ -10,8 +10,8 @@ extern "C" {
 int tq_nn11_grad_opt_step(tq_nn11_grad* h, int kind, double lr, double beta1, double beta2, double eps, double alpha, int64_t step,
                           float* const* weights, float* const* biases, const float* const* grad_w, const float* const* grad_b,
                           float* const* m_w, float* const* m_b, float* const* v_w, float* const* v_b, void* stream_) {
-    GHANDLE(h);
-    if (!h->loaded) return fail(TQ_E_INVALID, "nn11 optimizer step before tq_nn11_grad_load");
+    ENTER(h, "nn11 grad handle");
+    if (!h->net.loaded) return fail(TQ_E_INVALID, "nn11 optimizer step before tq_nn11_grad_load");
     if (const char* bad = tq::nn11_opt_bad_args(kind, lr, beta1, beta2, eps, alpha, step)) return fail(TQ_E_INVALID, "nn11 optimizer step: %s", bad);
     const bool adam = kind == TQ_OPT_ADAM;
     if (!weights || !biases || !grad_w || !grad_b || !v_w || !v_b) return fail(TQ_E_INVALID, "weights / biases / grad_w / grad_b / v_w / v_b is NULL");
@@ -28,8 +28,9 @@ int tq_nn11_grad_opt_step(tq_nn11_grad* h, int kind, double lr, double beta1, do
     const tq::NN11OptConsts c = tq::nn11_opt_consts(kind, lr, beta1, beta2, eps, alpha, step);
     // 144 blocks of 256 threads take the largest weight (128 x 128 x 9) in one pass of 16-byte groups
     const dim3 grid(144, tq::NN11_LAYERS + 1), block(256);
-    if (adam) return launch(tq::k_nn11_opt<tq::NN11_OPT_ADAM>, grid, block, stream, o, c, h->d, h->wimg, h->dimg, h->bias, h->limg, h->lbias);
-    return launch(tq::k_nn11_opt<tq::NN11_OPT_RMSPROP>, grid, block, stream, o, c, h->d, h->wimg, h->dimg, h->bias, h->limg, h->lbias);
+    const NN11Net& net = h->net;
+    if (adam) return launch(tq::k_nn11_opt<tq::NN11_OPT_ADAM>, grid, block, stream, o, c, h->d, net.wimg, net.dimg, net.bias, net.limg, net.lbias);
+    return launch(tq::k_nn11_opt<tq::NN11_OPT_RMSPROP>, grid, block, stream, o, c, h->d, net.wimg, net.dimg, net.bias, net.limg, net.lbias);
 }
 
 }  // extern "C"

@@ -33,11 +33,6 @@ int replay_latch(int flag) {
     return TQ_OK;
 }
 static_assert(offsetof(tq::ReplayDev, werr) == offsetof(tq::ReplayDev, err) + sizeof(int), "tq_replay_check reads the two latches as one");
-#define RHANDLE(r)                                                \
-    DeviceGuard _guard;                                           \
-    if (!(r)) return fail(TQ_E_INVALID, "NULL replay handle");    \
-    if (int _rc = _guard.enter_device((r)->device)) return _rc;   \
-    hipStream_t stream = (hipStream_t)stream_
 
 // canonical rebuild of the whole tree: every chunk, then the top levels
 int replay_rebuild_all(tq_replay* r, hipStream_t stream) {
@@ -109,18 +104,10 @@ int tq_replay_create(tq_replay** out, int d, int64_t capacity, double alpha, int
     return TQ_OK;
 }
 
-int tq_replay_destroy(tq_replay* r) {
-    if (!r) return TQ_OK;
-    DeviceGuard guard;
-    (void)guard.enter_device(r->device);
-    r->mem.release_all();
-    (void)hipGetLastError();
-    delete r;
-    return TQ_OK;
-}
+int tq_replay_destroy(tq_replay* r) { return destroy_handle(r); }
 
 int tq_replay_save_block(tq_replay* r, const void* block, int64_t cap, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (!block || cap < 0) return fail(TQ_E_INVALID, "bad block / cap");
     if (reinterpret_cast<uintptr_t>(block) & 7u) return fail(TQ_E_INVALID, "block must be 8-byte aligned");
     if (cap == 0) return TQ_OK;
@@ -152,7 +139,7 @@ int tq_replay_save_block(tq_replay* r, const void* block, int64_t cap, void* str
 }
 
 int64_t tq_replay_filled(tq_replay* r, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     int64_t filled = 0;
     HIPCHECK(hipMemcpyAsync(&filled, &r->st->filled, sizeof(int64_t), hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));
@@ -161,7 +148,7 @@ int64_t tq_replay_filled(tq_replay* r, void* stream_) {
 
 int tq_replay_get(tq_replay* r, const int64_t* indices, int n, float* state, float* next_state, int64_t* actions_idx,
                   float* rewards, uint8_t* terminals, int32_t* actions, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (n < 0 || (n > 0 && !indices)) return fail(TQ_E_INVALID, "bad indices / n");
     if (n == 0) return TQ_OK;
     tq::RingView ring = tq::ring_view(r->ring, r->w, r->cap);
@@ -175,7 +162,7 @@ int tq_replay_get(tq_replay* r, const int64_t* indices, int n, float* state, flo
 int tq_replay_sample(tq_replay* r, int batch, double beta, const double* uniforms, int64_t* indices, double* priorities,
                      double* weights, float* state, float* next_state, int64_t* actions_idx, float* rewards,
                      uint8_t* terminals, int32_t* actions, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (batch < 1 || batch > tq::RP_MAX_BATCH) return fail(TQ_E_INVALID, "batch must be in 1..%d (got %d)", tq::RP_MAX_BATCH, batch);
     if (!indices || !priorities || !weights) return fail(TQ_E_INVALID, "indices / priorities / weights is NULL");
     if (!(beta == beta)) return fail(TQ_E_INVALID, "beta is NaN");
@@ -189,7 +176,7 @@ int tq_replay_sample(tq_replay* r, int batch, double beta, const double* uniform
 }
 
 int tq_replay_next_persp_count(tq_replay* r, const int64_t* indices, int n, int32_t* counts, int64_t* offsets, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (int rc = replay_batch_ok(indices, n)) return rc;
     if (!offsets) return fail(TQ_E_INVALID, "offsets is NULL");
     REQUIRE_ALIGNED16(offsets, "offsets");
@@ -203,7 +190,7 @@ int tq_replay_next_persp_count(tq_replay* r, const int64_t* indices, int n, int3
 // scratch, and the writer checks the offsets against the planes it is given.
 int tq_replay_next_persp_write(tq_replay* r, const int64_t* indices, int n, const int64_t* offsets, void* out,
                                int32_t* positions, int64_t capacity, int dtype, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (int rc = replay_batch_ok(indices, n)) return rc;
     if (!offsets || !out) return fail(TQ_E_INVALID, "offsets / out is NULL");
     if (capacity < 0) return fail(TQ_E_INVALID, "negative capacity");
@@ -227,14 +214,14 @@ int tq_td_target(const float* q_table, const int64_t* offsets, int n, const floa
 }
 
 int tq_replay_update(tq_replay* r, const int64_t* indices, const double* priorities, int n, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (n < 0 || (n > 0 && (!indices || !priorities))) return fail(TQ_E_INVALID, "bad indices / priorities / n");
     if (n == 0) return TQ_OK;
     return replay_update(r, indices, priorities, n, stream);
 }
 
 int tq_replay_reset_alpha(tq_replay* r, double alpha, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (!(alpha >= 0.0) || alpha > 1e300) return fail(TQ_E_INVALID, "alpha must be a finite number >= 0");
     if (!r->faithful && r->alpha == 0.0) return fail(TQ_E_INVALID, "reset_alpha: alpha 0 cannot be inverted");
     if (int rc = launch_1d(tq::k_replay_realpha, r->cap, stream, leaves(r), r->st, r->alpha, alpha, r->faithful)) return rc;
@@ -243,7 +230,7 @@ int tq_replay_reset_alpha(tq_replay* r, double alpha, void* stream_) {
 }
 
 int tq_replay_leaves(tq_replay* r, double* out, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
     HIPCHECK(hipMemcpyAsync(out, leaves(r), (size_t)r->cap * sizeof(double), hipMemcpyDeviceToDevice, stream));
     return TQ_OK;
@@ -255,14 +242,14 @@ int64_t tq_replay_tree_nodes(const tq_replay* r) {
 }
 
 int tq_replay_tree(tq_replay* r, double* out, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
     HIPCHECK(hipMemcpyAsync(out, r->tree, (size_t)tq_replay_tree_nodes(r) * sizeof(double), hipMemcpyDeviceToDevice, stream));
     return TQ_OK;
 }
 
 int tq_replay_check(tq_replay* r, void* stream_) {
-    RHANDLE(r);
+    ENTER(r, "replay handle");
     int flags[2] = {0, 0};                                   // the replay kernels' latch, the stack writer's
     HIPCHECK(hipMemcpyAsync(flags, &r->st->err, sizeof(flags), hipMemcpyDeviceToHost, stream));
     HIPCHECK(hipStreamSynchronize(stream));

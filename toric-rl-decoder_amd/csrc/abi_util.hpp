@@ -116,6 +116,27 @@ struct DeviceGuard {
     ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
 };
 
+// How an entry point that takes a handle and a `void* stream_` begins: NULL is refused as "NULL <what>", the handle's
+// device is current until the entry point returns, and `stream` is the caller's stream.
+#define ENTER(h, what)                                            \
+    DeviceGuard _guard;                                           \
+    if (!(h)) return fail(TQ_E_INVALID, "NULL " what);            \
+    if (int _rc = _guard.enter_device((h)->device)) return _rc;   \
+    hipStream_t stream = (hipStream_t)stream_
+
+// tq_*_destroy of a handle whose device memory is all in its `mem` (a DeviceBuffers, below): NULL is fine, and a HIP
+// error of the frees does not stay behind as the runtime's sticky one.
+template <class H>
+int destroy_handle(H* h) {
+    if (!h) return TQ_OK;
+    DeviceGuard guard;
+    (void)guard.enter_device(h->device);
+    h->mem.release_all();
+    (void)hipGetLastError();
+    delete h;
+    return TQ_OK;
+}
+
 // Reads a device error latch (a word of ERR_* bits that kernels OR into) after everything queued on the stream,
 // and clears it if it was set.  The caller decodes *flag.
 int read_latch(int* device_word, hipStream_t stream, int* flag) {

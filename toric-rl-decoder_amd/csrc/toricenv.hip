@@ -181,11 +181,6 @@ struct tq_env {            // made by `new tq_env()`: what has no initialiser he
     DeviceBuffers mem;     // owns every device pointer above but lut (the device's, get_lut)
 };
 
-#define HANDLE(h)                                  \
-    DeviceGuard _guard;                            \
-    if (int _rc = _guard.enter(h)) return _rc;     \
-    hipStream_t stream = (hipStream_t)stream_
-
 extern "C" {
 
 int tq_version(void) { return TQ_VERSION; }
@@ -307,7 +302,7 @@ int tq_num_envs(const tq_env* h) { return h ? h->n : 0; }
 int tq_size(const tq_env* h) { return h ? h->d : 0; }
 
 int tq_reset_all(tq_env* h, const double* p_err, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (int rc = by_size(h->d, [&](auto D) {
             return launch_1d(tq::k_reset<D()>, h->n, stream, h->planes, h->episodes, h->steps, h->counts, nullptr, 0, p_err,
                              h->sched.p_default, h->seed, h->first_env, h->n, h->partial, h->mark, 0u, h->min_err, h->err);
@@ -317,7 +312,7 @@ int tq_reset_all(tq_env* h, const double* p_err, void* stream_) {
 }
 
 int tq_reset_idx(tq_env* h, const int32_t* idx, int n_idx, const double* p_err, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (n_idx < 0 || (n_idx > 0 && !idx)) return fail(TQ_E_INVALID, "bad idx / n_idx");
     if (n_idx == 0) return TQ_OK;
     if (++h->reset_epoch == 0) {                             // epoch 0 is the mark array's initial value
@@ -333,7 +328,7 @@ int tq_reset_idx(tq_env* h, const int32_t* idx, int n_idx, const double* p_err, 
 }
 
 int tq_step(tq_env* h, const int32_t* actions, float* rewards, uint8_t* terminals, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!actions) return fail(TQ_E_INVALID, "actions is NULL");
     REQUIRE_ALIGNED16(actions, "actions");
     if (int rc = by_size(h->d, [&](auto D) {
@@ -345,14 +340,14 @@ int tq_step(tq_env* h, const int32_t* actions, float* rewards, uint8_t* terminal
 }
 
 int tq_get_state(tq_env* h, uint8_t* out, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
     const int64_t total = (int64_t)h->n * 2 * h->d * h->d;
     return by_size(h->d, [&](auto D) { return launch_1d(tq::k_get_state<D()>, total, stream, h->planes, h->n, nullptr, h->n, out); });
 }
 
 int tq_get_state_idx(tq_env* h, const int32_t* idx, int n_idx, uint8_t* out, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (n_idx < 0 || (n_idx > 0 && (!idx || !out))) return fail(TQ_E_INVALID, "bad idx / out");
     if (n_idx == 0) return TQ_OK;
     const int64_t total = (int64_t)n_idx * 2 * h->d * h->d;
@@ -360,14 +355,14 @@ int tq_get_state_idx(tq_env* h, const int32_t* idx, int n_idx, uint8_t* out, voi
 }
 
 int tq_get_qubits(tq_env* h, uint8_t* out, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
     const int64_t total = (int64_t)h->n * 2 * h->d * h->d;
     return by_size(h->d, [&](auto D) { return launch_1d(tq::k_get_qubits<D()>, total, stream, h->planes, h->n, out); });
 }
 
 int tq_set_qubits(tq_env* h, const uint8_t* qubits, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!qubits) return fail(TQ_E_INVALID, "qubits is NULL");
     if (int rc = by_size(h->d, [&](auto D) {
             return launch_1d(tq::k_set_qubits<D()>, h->n, stream, h->planes, h->counts, qubits, h->n, h->partial);
@@ -377,26 +372,26 @@ int tq_set_qubits(tq_env* h, const uint8_t* qubits, void* stream_) {
 }
 
 int tq_get_counters(tq_env* h, uint32_t* episodes, uint32_t* steps, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (episodes) HIPCHECK(hipMemcpyAsync(episodes, h->episodes, 4 * (size_t)h->n, hipMemcpyDeviceToDevice, stream));
     if (steps) HIPCHECK(hipMemcpyAsync(steps, h->steps, 4 * (size_t)h->n, hipMemcpyDeviceToDevice, stream));
     return TQ_OK;
 }
 
 int tq_eval_ground_state(tq_env* h, uint8_t* out, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
     return by_size(h->d, [&](auto D) { return launch_1d(tq::k_flags<D()>, h->n, stream, h->planes, h->n, out, nullptr); });
 }
 
 int tq_is_terminal(tq_env* h, uint8_t* out, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!out) return fail(TQ_E_INVALID, "out is NULL");
     return by_size(h->d, [&](auto D) { return launch_1d(tq::k_flags<D()>, h->n, stream, h->planes, h->n, nullptr, out); });
 }
 
 int tq_persp_count(tq_env* h, int32_t* counts, int64_t* offsets, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!offsets) return fail(TQ_E_INVALID, "offsets is NULL");
     REQUIRE_ALIGNED16(offsets, "offsets");
     REQUIRE_ALIGNED16(counts, "counts");
@@ -445,7 +440,7 @@ int tq_stream_wait_event(tq_event* ev, void* stream_) {
 
 int tq_persp_write_range_signal(tq_env* h, const int64_t* offsets, int first, int count, void* out, int32_t* positions,
                                 int64_t capacity, int dtype, tq_event* done, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!offsets || !out) return fail(TQ_E_INVALID, "offsets / out is NULL");
     if (capacity < 0) return fail(TQ_E_INVALID, "negative capacity");
     if (first < 0 || count < 0 || (int64_t)first + count > h->n) return fail(TQ_E_INVALID, "lattice range outside [0, n_envs)");
@@ -622,7 +617,7 @@ int tq_states_select_action(int n, const float* q_table, const int64_t* offsets,
 
 int tq_select_action(tq_env* h, const float* q_table, const int64_t* offsets, const int32_t* positions,
                      const double* eps, int32_t* actions, float* q_values, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!offsets || !positions || !actions) return fail(TQ_E_INVALID, "offsets / positions / actions is NULL");
     if (q_table && !eps) return fail(TQ_E_INVALID, "eps is NULL");
     return by_size(h->d, [&](auto D) {
@@ -646,7 +641,7 @@ int64_t tq_transition_block_bytes(int d, int64_t cap) {
 // the packed block this goes through is the handle's own scratch (allocated by tq_create)
 int tq_transition_write(tq_env* h, const int32_t* actions, uint8_t* persp, uint8_t* next_persp,
                         int32_t* actions_out, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     if (!actions) return fail(TQ_E_INVALID, "actions is NULL");
     REQUIRE_ALIGNED16(actions, "actions");
     REQUIRE_ALIGNED16(actions_out, "actions_out");
@@ -686,7 +681,7 @@ int tq_transition_unpack(int d, const void* block, int64_t cap, int64_t first, i
 
 int tq_actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float* rewards, uint8_t* terminals,
                   void* block, int64_t block_cap, int64_t slot_base, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     REQUIRE_ALIGNED16(actions, "actions");
     REQUIRE_ALIGNED16(actions_out, "actions_out");
     if (block && (reinterpret_cast<uintptr_t>(block) & 7u)) return fail(TQ_E_INVALID, "block must be 8-byte aligned");
@@ -707,7 +702,7 @@ int tq_actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float
 }
 
 int tq_check(tq_env* h, void* stream_) {
-    HANDLE(h);
+    ENTER(h, "handle");
     int flag;
     if (int rc = read_latch(h->err, stream, &flag)) return rc;
     return decode_latch(flag);
