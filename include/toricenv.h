@@ -213,6 +213,32 @@ int tq_select_action(tq_env* h, const float* q_table, const int64_t* offsets,
                      const int32_t* positions, const double* eps, int32_t* actions,
                      float* q_values, void* stream);
 
+/* ---- The planned selection: the forward pass on the perspectives the selection reads only.  Design: DESIGN.md 3.9.
+ * tq_select_action decides before it looks at a Q-value whether lattice e acts greedily -- (1-eps[e]) > U, one Philox
+ * draw keyed by the lattice's (episode, step) -- and a lattice that does not reads ONE row of the Q-table (the row of the
+ * perspective it drew, for q_values), a greedy lattice all n_e of its rows, a lattice without perspectives none.  Three
+ * calls on one stream, with no tq_step / tq_actor_step / tq_reset_* of the handle between the first and the last:
+ *   tq_select_plan            -> the list of those rows
+ *   tq_nn11_forward_rows      -> q_rows f32[R][3], the Q-values of the listed rows of the stack
+ *   tq_select_action_planned  -> the actions and q_values tq_select_action gives on the full table, bit for bit
+ *
+ * tq_select_plan: offsets i64[N+1] (tq_persp_count), eps f64[N] -> plan_offsets i64[N+1] (16-byte aligned; the exclusive
+ * scan of need[e] = 0 | n_e | 1; R = plan_offsets[N], which the caller reads back to size the forward) and rows
+ * i32[min(R, rows_cap)]: lattice by lattice, offsets[e] .. offsets[e+1]-1 of a greedy lattice, offsets[e] + the drawn
+ * perspective of another -- strictly increasing.  rows_cap >= P always suffices.  When R > rows_cap nothing is written at
+ * or past rows_cap and TQ_E_CAPACITY is latched; offsets whose differences lie outside [0, 2*d*d] latch TQ_E_INVALID
+ * (tq_check reports both).  The scratch is the handle's: the call never allocates; one such call per handle at a time. */
+int tq_select_plan(tq_env* h, const int64_t* offsets, const double* eps, int64_t* plan_offsets,
+                   int32_t* rows, int64_t rows_cap, void* stream);
+/* tq_select_action over the compact table: q_rows f32[R,3] (row i = the Q-values of perspective rows[i]), offsets and
+ * positions i32[P,3] of the FULL stack, plan_offsets from tq_select_plan, the same eps -> actions i32[N,4], q_values
+ * f32[N,3] (may be NULL).  It draws again with the same counters.  A lattice whose slice of the plan is not as long as this
+ * eps and the handle's current counters need -- another eps, or a step between plan and selection -- gets action 0 and
+ * zero q_values, reads nothing of q_rows, and TQ_E_INVALID is latched (tq_check). */
+int tq_select_action_planned(tq_env* h, const float* q_rows, const int64_t* offsets,
+                             const int64_t* plan_offsets, const int32_t* positions, const double* eps,
+                             int32_t* actions, float* q_values, void* stream);
+
 /* The same selection for an explicit batch of states that does not live in a handle --
  * selectActionBatch(number_of_actions, epsilon, grid_shift, toric_size, state, model, device)
  * (numba/util_actor.py:11-53) after the model forward.  The reference draws from numpy's global,
@@ -310,7 +336,7 @@ int tq_actor_step(tq_env* h, const int32_t* actions, int32_t* actions_out, float
 
 /* Reads and clears the handle's device error latch (synchronises `stream`): 0, TQ_E_ACTION,
  * TQ_E_CAPACITY, TQ_E_INDEX, TQ_E_RESET or TQ_E_INVALID (offsets handed to tq_persp_write that are not the scan of the
- * lattices' counts). */
+ * lattices' counts, or a tq_select_action_planned whose plan was made with another eps or before a step). */
 int tq_check(tq_env* h, void* stream);
 
 /* ---- Prioritized replay memory on the device (PrioritizedReplayMemory / SumTree, src/ReplayMemory.py:45-152,
@@ -410,6 +436,15 @@ int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* bi
  * TQ_U8, 16-byte aligned) -> q f32[rows][3].  Any rows >= 0: the call walks passes of max_rows itself.  TQ_E_INVALID
  * before the first tq_nn11_load. */
 int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
+/* model(stack[rows]): q[i] = the Q-values of perspective rows[i] of stack[stack_rows][2][d][d], i < n, read in place by
+ * conv1 -- the same bits as tq_nn11_forward's q[rows[i]].  rows: device i32[n], any list: unsorted, with repeats.  Any
+ * n >= 0 (passes of max_rows, like tq_nn11_forward); the same arguments are refused before any launch, and a NULL rows
+ * or negative stack_rows.  An index outside [0, stack_rows) reads nothing: its q row is that of an all-zero perspective,
+ * every other row is unaffected, and TQ_E_INDEX is latched for tq_nn11_check. */
+int tq_nn11_forward_rows(tq_nn11* h, const void* stack, int dtype, int64_t stack_rows, const int32_t* rows,
+                         int64_t n, float* q, void* stream);
+/* Reads and clears the forward handle's device error latch (synchronises `stream`): 0 or TQ_E_INDEX. */
+int tq_nn11_check(tq_nn11* h, void* stream);
 
 /* ---- NN_11's learner step (src/Learner_mp.py:140-169): the forward with every layer's output kept, the gather of
  * Q(s,a), the weighted squared error, the backward pass and the parameter gradients.  The optimizer works on the caller's

@@ -61,6 +61,8 @@ SYMBOLS = [
     ("tq_states_persp_write", _i, [_i, _i, _vp, _vp, _vp, _vp, _i64, _i, _vp]),
     ("tq_select_action", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tq_states_select_action", _i, [_i, _vp, _vp, _vp, _vp, _u64, _u64, _i64, _vp, _vp, _vp]),
+    ("tq_select_plan", _i, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    ("tq_select_action_planned", _i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     ("tq_states_check", _i, [_vp]),
     ("tq_segment_max", _i, [_vp, _vp, _i, _vp, _vp, _vp]),
     ("tq_td_target", _i, [_vp, _vp, _i, _vp, _vp, C.c_float, C.c_float, C.c_float, _vp, _vp]),
@@ -89,6 +91,8 @@ SYMBOLS = [
     ("tq_nn11_destroy", _i, [_vp]),
     ("tq_nn11_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     ("tq_nn11_forward", _i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    ("tq_nn11_forward_rows", _i, [_vp, _vp, _i, _i64, _vp, _i64, _vp, _vp]),
+    ("tq_nn11_check", _i, [_vp, _vp]),
     ("tq_nn11_grad_create", _i, [C.POINTER(_vp), _i, _i, _i]),
     ("tq_nn11_grad_destroy", _i, [_vp]),
     ("tq_nn11_grad_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),

@@ -144,7 +144,7 @@ def computePrioritiesParallel(A, R, Q, Qns, discount):
 
 
 def run_actor(envs, model, n_flushes, size_local_memory_buffer, epsilon, discount_factor=0.95, sink=None,
-              chunk=1 << 16, weight_sync=None):
+              chunk=1 << 16, weight_sync=None, sparse=False):
     """Runs `n_flushes` buffer flushes of the actor loop on `envs` (an EnvSet with numpy_io=False,
     already reset).  Yields one TransitionBlock per flush: no_envs * size_local_memory_buffer
     transitions in slot order t * no_envs + e with their priorities in the block's priority section
@@ -154,7 +154,8 @@ def run_actor(envs, model, n_flushes, size_local_memory_buffer, epsilon, discoun
     priorities of the column before it, and its transition is not recorded.
     ``weight_sync``: called with the model when the buffer is full, before the priorities and the send --
     where upstream loads the learner's new weights (Actor_mp.py:133-144); on N>1 pass
-    ``lambda m: gather.broadcast_weights(m, src=learner_rank)``."""
+    ``lambda m: gather.broadcast_weights(m, src=learner_rank)``.
+    ``sparse``: selectActionEnvSet's -- the policy's forward on the perspectives the selection reads only."""
     assert not envs.numpy_io, "run_actor needs an EnvSet with numpy_io=False"
     n, dev = envs.no_envs, envs.device
     T = int(size_local_memory_buffer)
@@ -163,7 +164,7 @@ def run_actor(envs, model, n_flushes, size_local_memory_buffer, epsilon, discoun
     for f in range(n_flushes):
         blk = blocks[f & 1]
         for t in range(T + 1):
-            act, qv = selectActionEnvSet(envs, model, epsilon, chunk=chunk)
+            act, qv = selectActionEnvSet(envs, model, epsilon, chunk=chunk, sparse=sparse)
             Q[t] = qv
             envs.actorStep(act, block=blk if t < T else None, slot=t)
         if weight_sync is not None:

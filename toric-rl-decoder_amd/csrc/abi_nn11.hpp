@@ -45,16 +45,20 @@ struct NN11Net {
 
 // One convolution over `rows` perspectives.  Every k_nn11_conv the library holds is in the list below, by (k-steps,
 // n-tiles, mode): five shapes of the forward (EPI = NN11_EPI_BIAS_RELU, `aux` the padded bias) and four of the dgrad
-// (NN11_EPI_MASK, `aux` the activation image whose sign masks).
-template <int D, int EPI>
+// (NN11_EPI_MASK, `aux` the activation image whose sign masks); and conv1 once more with GATHER, whose perspectives are
+// the rows `g` lists of the stack `in`.
+template <int D, int EPI, typename... ROWS>
 int nn11_conv(int mode, int ks, int nt, const void* in, int dtype, const uint16_t* img, const void* aux, uint16_t* out, int64_t rows,
-              hipStream_t stream) {
+              hipStream_t stream, ROWS... g) {
+    constexpr bool GATHER = sizeof...(ROWS) != 0;
     constexpr int G = tq::NN11Geom<D>::G, THREADS = tq::NN11Geom<D>::THREADS;
     const dim3 grid((unsigned)((rows + G - 1) / G)), block(THREADS);
 #define NN11_SHAPE(KS, NT, MODE)                         \
     if (ks == KS && nt == NT && mode == tq::MODE)        \
-        return launch(tq::k_nn11_conv<D, KS, NT, tq::MODE, EPI>, grid, block, stream, in, dtype, img, aux, out, rows)
-    if constexpr (EPI == tq::NN11_EPI_BIAS_RELU) {
+        return launch(tq::k_nn11_conv<D, KS, NT, tq::MODE, EPI, GATHER, ROWS...>, grid, block, stream, in, dtype, img, aux, out, rows, g...)
+    if constexpr (GATHER) {
+        NN11_SHAPE(2, 4, NN11_CIRCULAR);
+    } else if constexpr (EPI == tq::NN11_EPI_BIAS_RELU) {
         NN11_SHAPE(2, 4, NN11_CIRCULAR);
         NN11_SHAPE(6, 2, NN11_VALID);
         NN11_SHAPE(8, 4, NN11_ZERO);
@@ -71,11 +75,16 @@ int nn11_conv(int mode, int ks, int nt, const void* in, int dtype, const uint16_
 }
 
 // The forward of `rows` perspectives: conv l = 1..11 writes its bf16 image to out[l] (conv1 reads the stack, conv l
-// reads out[l - 1]), the linear layer reads out[11] and writes q.
-template <int D>
-int nn11_forward(const NN11Net& net, const void* stack, int dtype, int64_t rows, uint16_t* const* out, float* q, hipStream_t stream) {
+// reads out[l - 1]), the linear layer reads out[11] and writes q.  GATHER: perspective i is row g.rows[i] of the stack.
+template <int D, typename... ROWS>
+int nn11_forward(const NN11Net& net, const void* stack, int dtype, int64_t rows, uint16_t* const* out, float* q, hipStream_t stream,
+                 ROWS... g) {
     constexpr int L = tq::NN11_LAYERS;
-    for (int l = 1; l <= L; ++l)
+    constexpr bool GATHER = sizeof...(ROWS) != 0;
+    if constexpr (GATHER)
+        if (int rc = nn11_conv<D, tq::NN11_EPI_BIAS_RELU>(tq::nn11_mode(1), tq::nn11_ksteps(1), tq::nn11_ntiles(1), stack, dtype,
+                                                          net.wimg, net.bias, out[1], rows, stream, g...)) return rc;
+    for (int l = GATHER ? 2 : 1; l <= L; ++l)
         if (int rc = nn11_conv<D, tq::NN11_EPI_BIAS_RELU>(tq::nn11_mode(l), tq::nn11_ksteps(l), tq::nn11_ntiles(l),
                                                           l == 1 ? stack : out[l - 1], l == 1 ? dtype : 0,
                                                           net.wimg + tq::nn11_wimg_offset(l), net.bias + tq::nn11_bias_offset(l),
@@ -91,6 +100,7 @@ struct tq_nn11 {                           // made by `new tq_nn11()`: every mem
     NN11Net net;
     uint16_t* act[2];                      // activation images of one pass, taking turns: max_rows * d^2 * 128 bf16 each
     uint16_t* out[tq::NN11_LAYERS + 1];    // out[l], l = 1..11: the one of the two that layer l writes
+    int* latch;                            // device error latch of tq_nn11_forward_rows (NN11_ERR_INDEX)
     DeviceBuffers mem;
 };
 
@@ -113,6 +123,7 @@ int tq_nn11_create(tq_nn11** out, int d, int64_t max_rows, int device) {
     for (int i = 0; i < 2; ++i)
         h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::NN11_MAX_CP * sizeof(uint16_t));
     for (int l = 1; l <= tq::NN11_LAYERS; ++l) h->out[l] = h->act[(l + 1) & 1];
+    h->mem.zeroed(&h->latch, 16);
     hipError_t e = h->mem.err;
     if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) { tq_nn11_destroy(h); return fail(TQ_E_HIP, "nn11 allocation failed: %s", hipGetErrorString(e)); }
@@ -125,15 +136,23 @@ int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* bi
     return h->net.load(h->d, weights, biases, stream);
 }
 
-int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream_) {
-    ENTER(h, "nn11 handle");
+// what both forwards refuse before any launch; *done: nothing to do (no rows)
+static int nn11_forward_args(const tq_nn11* h, const void* stack, int dtype, int64_t rows, const float* q, bool* done) {
+    *done = false;
     if (!h->net.loaded) return fail(TQ_E_INVALID, "nn11 forward before tq_nn11_load");
     if (dtype < TQ_F32 || dtype > TQ_U8) return fail(TQ_E_INVALID, "bad stack dtype %d", dtype);
     if (rows < 0) return fail(TQ_E_INVALID, "negative rows");
-    if (rows == 0) return TQ_OK;
+    if (rows == 0) { *done = true; return TQ_OK; }
     if (!stack || !q) return fail(TQ_E_INVALID, "stack / q is NULL");
     REQUIRE_ALIGNED16(stack, "stack");
     REQUIRE_ALIGNED16(q, "q");
+    return TQ_OK;
+}
+
+int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream_) {
+    ENTER(h, "nn11 handle");
+    bool done;
+    if (int rc = nn11_forward_args(h, stack, dtype, rows, q, &done); rc || done) return rc;
     const int64_t esize = dtype == TQ_F32 ? 4 : (dtype == TQ_U8 ? 1 : 2);
     const int64_t row_bytes = 2 * (int64_t)h->d * h->d * esize;
     return by_size(h->d, [&](auto D) {                     // passes of at most max_rows perspectives
@@ -144,6 +163,31 @@ int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, floa
         }
         return (int)TQ_OK;
     });
+}
+
+int tq_nn11_forward_rows(tq_nn11* h, const void* stack, int dtype, int64_t stack_rows, const int32_t* rows, int64_t n, float* q,
+                         void* stream_) {
+    ENTER(h, "nn11 handle");
+    bool done;
+    if (int rc = nn11_forward_args(h, stack, dtype, n, q, &done); rc || done) return rc;
+    if (stack_rows < 0) return fail(TQ_E_INVALID, "negative stack_rows");
+    if (!rows) return fail(TQ_E_INVALID, "rows is NULL");
+    return by_size(h->d, [&](auto D) {                     // passes of at most max_rows perspectives, all over the one stack
+        for (int64_t first = 0; first < n; first += h->max_rows) {
+            const int64_t m = n - first < h->max_rows ? n - first : h->max_rows;
+            if (int rc = nn11_forward<D()>(h->net, stack, dtype, m, h->out, q + first * tq::NN11_OUT, stream,
+                                           tq::NN11Rows{rows + first, stack_rows, h->latch})) return rc;
+        }
+        return (int)TQ_OK;
+    });
+}
+
+int tq_nn11_check(tq_nn11* h, void* stream_) {
+    ENTER(h, "nn11 handle");
+    int flag;
+    if (int rc = read_latch(h->latch, stream, &flag)) return rc;
+    if (flag & tq::NN11_ERR_INDEX) return fail(TQ_E_INDEX, "tq_nn11_forward_rows: a row index outside [0, stack_rows) was given");
+    return TQ_OK;
 }
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 
 #include "env_step.hpp"
 #include "scan.hpp"
+#include "select_plan.hpp"
 #include "td_target.hpp"
 
 namespace tq {
@@ -500,8 +501,8 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ q, con
         return;
     }
     // handle-bound: counters = the lattice's (episode, step); stateless: the caller's call counter
-    const U4 w = draw(seed, (uint32_t)(first_env + e), episodes ? episodes[e] : c1, steps ? steps[e] : c2, domain, 0);
-    const bool greedy = q != nullptr && (1.0 - eps[e]) > u01(w.x);
+    const U4 w = sel_draw(seed, (uint32_t)(first_env + e), episodes ? episodes[e] : c1, steps ? steps[e] : c2, domain);
+    const bool greedy = q != nullptr && sel_greedy(w, eps[e]);
     int pidx, a;
     if (greedy) {
         float best = -__builtin_inff();
@@ -519,8 +520,8 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ q, con
         bk = bk == 0x7fffffff ? 0 : bk;
         pidx = bk / 3; a = bk - 3 * pidx;
     } else {
-        pidx = (int)mulhi32(w.y, (uint32_t)n);
-        a = (int)mulhi32(w.z, 3);
+        pidx = sel_random_persp(w, n);
+        a = sel_random_op(w);
     }
     if (lane < 3) {
         actions[4 * e + lane] = pos[3 * (lo + pidx) + lane];

@@ -193,6 +193,11 @@ typedef float nn11_f32x16 __attribute__((ext_vector_type(16)));
 
 struct NN11Pack { const float* w[NN11_LAYERS + 1]; const float* b[NN11_LAYERS + 1]; };
 
+// The one more argument of a gathering k_nn11_conv: the row list.
+constexpr int NN11_ERR_INDEX = 1;                         // the forward handle's latch: a row index outside the stack was seen
+struct NN11Rows { const int32_t* rows; int64_t stack_rows; int* latch; };
+__device__ __forceinline__ const NN11Rows& nn11_rows_arg(const NN11Rows& g) { return g; }
+
 // one block row (blockIdx.y) per layer: y = 0..10 conv l = y + 1 (image, then its padded bias); y = 11 the linear layer
 __global__ __launch_bounds__(256) void k_nn11_pack(NN11Pack p, int d, uint16_t* wimg, float* bias, float* limg, float* lbias) {
     const int l = (int)blockIdx.y + 1;
@@ -227,9 +232,14 @@ __device__ __forceinline__ uint16_t nn11_stack_bf16(const void* stack, int dtype
 // EPI says what becomes of the sums.  NN11_EPI_BIAS_RELU (the forward): `aux` is the layer's padded f32 bias;
 // out = bf16(relu(sum + bias)).  NN11_EPI_MASK (the backward's dgrad over a dgrad image; NN11_FULL reads a (d-2)^2
 // image): `aux` is the bf16 activation image of `out`'s shape; out = bf16(sum where the activation is > 0, else 0).
-template <int D, int KS, int NT, int MODE, int EPI = NN11_EPI_BIAS_RELU>
+// GATHER (conv1 only; ROWS is then NN11Rows, one more argument `g`, and empty otherwise, so that the kernels without it
+// keep their argument list): perspective i of the call is row g.rows[i] of the stack `in` -- any list, unsorted, with
+// repeats.  An index outside [0, g.stack_rows) stages zeros, reads nothing and sets NN11_ERR_INDEX in g.latch.
+template <int D, int KS, int NT, int MODE, int EPI = NN11_EPI_BIAS_RELU, bool GATHER = false, typename... ROWS>
 __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nn11_conv(const void* __restrict__ in, int dtype, const uint16_t* __restrict__ wimg,
-                                                   const void* __restrict__ aux, uint16_t* __restrict__ out, int64_t P) {
+                                                   const void* __restrict__ aux, uint16_t* __restrict__ out, int64_t P, ROWS... rows_arg) {
+    static_assert(!GATHER || MODE == NN11_CIRCULAR, "only conv1 reads the stack");
+    static_assert(sizeof...(ROWS) == (GATHER ? 1 : 0), "a gathering conv takes one NN11Rows, the others nothing");
     using Ge = NN11Geom<D>;
     constexpr int PIX = Ge::PIX, G = Ge::G, MW = Ge::MW, NW = Ge::NW, THREADS = Ge::THREADS;
     constexpr int NPIX_OUT = MODE == NN11_VALID ? Ge::OPIX : PIX;
@@ -250,8 +260,22 @@ __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nn11_conv(const void* 
 
     if constexpr (MODE == NN11_CIRCULAR) {
         uint16_t* s = reinterpret_cast<uint16_t*>(lds);
-        for (int i = tid; i < G * 2 * PIX; i += THREADS)
-            s[i] = i < np * 2 * PIX ? nn11_stack_bf16(in, dtype, persp0 * 2 * PIX + i) : (uint16_t)0;
+        if constexpr (GATHER) {
+            const NN11Rows& g = nn11_rows_arg(rows_arg...);
+            for (int i = tid; i < G * 2 * PIX; i += THREADS) {
+                uint16_t v = 0;
+                if (i < np * 2 * PIX) {
+                    const int p = i / (2 * PIX), c = i - p * (2 * PIX);
+                    const int64_t row = g.rows[persp0 + p];
+                    if (row >= 0 && row < g.stack_rows) v = nn11_stack_bf16(in, dtype, row * (2 * PIX) + c);
+                    else if (c == 0) atomicOr(g.latch, NN11_ERR_INDEX);
+                }
+                s[i] = v;
+            }
+        } else {
+            for (int i = tid; i < G * 2 * PIX; i += THREADS)
+                s[i] = i < np * 2 * PIX ? nn11_stack_bf16(in, dtype, persp0 * 2 * PIX + i) : (uint16_t)0;
+        }
     } else {
         const uint4* src = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(in) + persp0 * NPIX_IN * CINP);
         constexpr int CH16 = CINP / 8;                                      // 16-byte chunks per row

@@ -10,6 +10,7 @@
 
 #include "abi_util.hpp"
 #include "stream_write.hpp"
+#include "select_kernels.hpp"
 #include "replay.hpp"
 
 namespace {
@@ -48,7 +49,8 @@ int decode_latch(int flag) {
     if (flag & tq::ERR_CAPACITY) return fail(TQ_E_CAPACITY, "perspective stack capacity exceeded");
     if (flag & tq::ERR_INTERNAL)
         return fail(TQ_E_INVALID, "stack write refused: the offsets are not the scan of these lattices' perspective counts "
-                                  "(stale, shifted or from another batch), or a wave gave up waiting");
+                                  "(stale, shifted or from another batch), or a wave gave up waiting; or a planned selection "
+                                  "whose plan was made with another eps or before a step");
     if (flag & tq::ERR_INDEX) return fail(TQ_E_INDEX, "tq_reset_idx: an index outside [0, n_envs) was given");
     if (flag & tq::ERR_RESET_DUP) return fail(TQ_E_INDEX, "tq_reset_idx: an index was listed more than once");
     if (flag & tq::ERR_RESET_ROUNDS)
@@ -178,6 +180,8 @@ struct tq_env {            // made by `new tq_env()`: what has no initialiser he
     unsigned int* slots;   // N_SLOT_SETS sets of STREAM_SLOT_WORDS counters: the workgroups of a stack write take their shares by XCD (stream_write.hpp)
     unsigned write_seq;    // and leave them zero; write i uses set i % N, so N writes of one handle may be in flight
     int xcd_bias = -1;     // this handle's share setting (tq_env_set_xcd_bias), or -1: the process-wide one
+    int32_t* sel_need;     // [N] scratch of tq_select_plan: rows of the Q-table each lattice's selection reads,
+    int64_t* sel_partial;  // and the level-1 sums of their scan
     DeviceBuffers mem;     // owns every device pointer above but lut (the device's, get_lut)
 };
 
@@ -235,6 +239,8 @@ int tq_create(tq_env** out, int n_envs, int d, int device, uint64_t seed, int64_
     m.zeroed(&h->tblock, (size_t)tq::block_bytes(h->w, n_envs));
     for (int32_t*& t : h->split) m.zeroed(&t, (size_t)tq::cut_table_words(SPLIT_LG) * sizeof(int32_t));
     m.zeroed(&h->slots, N_SLOT_SETS * tq::STREAM_SLOT_WORDS * sizeof(unsigned int));
+    m.zeroed(&h->sel_need, N * 4 + 32);                         // +32: as for counts
+    m.zeroed(&h->sel_partial, ((N + tq::PART_BLOCK - 1) / tq::PART_BLOCK) * 8);
     if (const hipError_t e = m.err; e != hipSuccess) { tq_destroy(h); return fail(TQ_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
     if (int rc = get_lut(device, d, nullptr, &h->lut)) { tq_destroy(h); return rc; }
     h->num_cus = g_ctx[device].num_cus;
@@ -623,6 +629,33 @@ int tq_select_action(tq_env* h, const float* q_table, const int64_t* offsets, co
     return by_size(h->d, [&](auto D) {
         return launch_1d(tq::k_select<D()>, (int64_t)h->n * 64, stream, q_table, offsets, positions, eps, h->episodes, h->steps,
                          0u, 0u, tq::DOMAIN_SEL, actions, q_values, h->seed, h->first_env, h->n);
+    });
+}
+
+// select_plan.hpp: need -> scan -> rows.  The scratch is the handle's (tq_create); nothing is allocated here.
+int tq_select_plan(tq_env* h, const int64_t* offsets, const double* eps, int64_t* plan_offsets, int32_t* rows, int64_t rows_cap,
+                   void* stream_) {
+    ENTER(h, "handle");
+    if (!offsets || !eps || !plan_offsets) return fail(TQ_E_INVALID, "offsets / eps / plan_offsets is NULL");
+    if (rows_cap < 0 || (rows_cap > 0 && !rows)) return fail(TQ_E_INVALID, "bad rows / rows_cap");
+    REQUIRE_ALIGNED16(plan_offsets, "plan_offsets");
+    return by_size(h->d, [&](auto D) {
+        if (int rc = launch_1d(tq::k_select_need<D()>, h->n, stream, offsets, eps, h->episodes, h->steps, h->sel_need, h->seed,
+                               h->first_env, h->n, h->sel_partial, h->err)) return rc;
+        if (int rc = launch_scan(h->sel_need, h->sel_partial, true, plan_offsets, nullptr, h->n, stream, nullptr)) return rc;
+        return launch_1d(tq::k_select_rows<D()>, (int64_t)h->n * 64, stream, offsets, plan_offsets, eps, h->episodes, h->steps, rows,
+                         rows_cap, h->seed, h->first_env, h->n, h->err);
+    });
+}
+
+int tq_select_action_planned(tq_env* h, const float* q_rows, const int64_t* offsets, const int64_t* plan_offsets,
+                             const int32_t* positions, const double* eps, int32_t* actions, float* q_values, void* stream_) {
+    ENTER(h, "handle");
+    if (!q_rows || !offsets || !plan_offsets || !positions || !eps || !actions)
+        return fail(TQ_E_INVALID, "q_rows / offsets / plan_offsets / positions / eps / actions is NULL");
+    return by_size(h->d, [&](auto D) {
+        return launch_1d(tq::k_select_planned<D()>, (int64_t)h->n * 64, stream, q_rows, offsets, plan_offsets, positions, eps,
+                         h->episodes, h->steps, actions, q_values, h->seed, h->first_env, h->n, h->err);
     });
 }
 

@@ -107,6 +107,17 @@ def make(env_id, config=None, device=None, seed=0):
     return ToricEnv(config, device=device, seed=seed)
 
 
+class SelectPlan:
+    """What EnvSet.selectPlan returns: ``rows`` int32 (R,), the perspectives (rows of the stack / the Q-table) the
+    epsilon-greedy selection of the current step reads, strictly increasing; ``plan_offsets`` int64 (N+1,), lattice e's
+    slice of them; ``R`` their number.  Views of buffers the EnvSet re-uses: valid until its next selectPlan."""
+
+    __slots__ = ("rows", "plan_offsets", "R")
+
+    def __init__(self, rows, plan_offsets, R):
+        self.rows, self.plan_offsets, self.R = rows, plan_offsets, R
+
+
 class EnvSet(Handle):
     """Batch of N toric-code lattices resident on one MI355X (reference: src/EnvSet.py:4-51).
 
@@ -121,6 +132,8 @@ class EnvSet(Handle):
         self._parked = []               # candidates pickStackBuffer(park=True) rejected, until releaseParked() / close()
         self._stack_cache = None        # generatePerspectiveReused's buffer: dict(dtype, capacity, buf, pos, probe)
         self._positions = None          # positions of the last stack written: selectAction's default
+        self._plan_rows = None          # selectPlan's row list (grown when a step needs more) and plan offsets
+        self._plan_offsets = None
         self._h = C.c_void_p(None)
         self.size = int(env.system_size)
         self.no_envs = int(no_envs)
@@ -160,6 +173,7 @@ class EnvSet(Handle):
     def close(self):
         self._parked = []
         self._stack_cache = None
+        self._plan_rows = self._plan_offsets = None
         super().close()
 
     def _out(self, x, dtype=None):
@@ -412,15 +426,53 @@ class EnvSet(Handle):
         return self._out(out), self._out(pos, np.int64), self._out(counts, np.int64)
 
     # ------------------------------------------------------------------ policy glue
-    def selectAction(self, q_table, eps, positions=None, offsets=None):
+    def _eps(self, eps):
+        """a scalar or (N,) epsilon -> float64 (N,) on the device"""
+        if not torch.is_tensor(eps):
+            eps = np.broadcast_to(np.asarray(eps, np.float64), (self.no_envs,))
+        e = to_device(eps, torch.float64, self.device)
+        if e.numel() != self.no_envs:
+            raise ValueError("eps must be a scalar or have one entry per env")
+        return e
+
+    def selectPlan(self, eps, offsets=None):
+        """Which rows of the Q-table selectAction(q, eps) would read, decided before any Q-value exists (tq_select_plan):
+        all n of a lattice that will act greedily, the one row of a lattice that will not, none of a lattice without
+        perspectives -> a SelectPlan.  The forward pass then runs on ``plan.rows`` alone and
+        ``selectAction(q_rows, eps, plan=plan)`` selects from its (R, 3) output, with the same result in bits.  No step or
+        reset may lie between the plan and that selection, and ``eps`` must be the same (check() raises otherwise).
+        ``offsets``: default the last perspectiveCounts.  Reads R back (one 8-byte copy: the row count is data dependent)."""
+        off = self._offsets if offsets is None else to_device(offsets, torch.int64, self.device)
+        e = self._eps(eps)
+        n = self.no_envs
+        cap = self._positions.shape[0] if self._positions is not None else n * 2 * self.size * self.size
+        if self._plan_rows is None or self._plan_rows.numel() < cap:
+            self._plan_rows = torch.empty(max(cap, 1024), dtype=torch.int32, device=self.device)
+        if self._plan_offsets is None:
+            self._plan_offsets = torch.zeros(n + 2, dtype=torch.int64, device=self.device)[:n + 1]
+        rows, poff = self._plan_rows, self._plan_offsets
+        self._call(self._L.tq_select_plan, _ptr(off), _ptr(e), _ptr(poff), _ptr(rows), rows.numel())
+        R = int(poff[-1].item())
+        return SelectPlan(rows[:R], poff, R)
+
+    def selectAction(self, q_table, eps, positions=None, offsets=None, plan=None):
         """_selectActionBatch_prime on the device -> (actions (N,4), q_values (N,3)).
-        q_table None = pure exploration (every eps must be 1)."""
+        q_table None = pure exploration (every eps must be 1).
+        ``plan`` (a SelectPlan of this step and this eps): ``q_table`` is the compact (R, 3) table of ``plan.rows``."""
         pos = self._positions if positions is None else positions
         if pos is None:
             raise ValueError("call generatePerspective / writePerspectives (with positions) first")
         pos = to_device(pos, torch.int32, self.device)
         off = self._offsets if offsets is None else to_device(offsets, torch.int64, self.device)
         q = to_device(q_table, torch.float32, self.device)
+        if plan is not None:
+            if q is None or q.numel() != 3 * plan.R:
+                raise ValueError("with a plan, q_table must be the (plan.R, 3) table of plan.rows")
+            if plan.R == 0:                                     # no lattice has a perspective: nothing of q is read
+                q = torch.zeros((1, 3), dtype=torch.float32, device=self.device)
+            self._call(self._L.tq_select_action_planned, _ptr(q), _ptr(off), _ptr(plan.plan_offsets), _ptr(pos),
+                       _ptr(self._eps(eps)), _ptr(self._actions), _ptr(self._qv))
+            return self._out(self._actions, np.int64), self._out(self._qv)
         if q is not None and not torch.is_tensor(eps):
             eps = np.broadcast_to(np.asarray(eps, np.float64), (self.no_envs,))
         e = None if q is None else to_device(eps, torch.float64, self.device)

@@ -104,13 +104,29 @@ class NN11Forward(Handle):
         self._call(self._L.tq_nn11_load, _pointers(w), _pointers(b))   # the pack kernel reads w / b on the current stream,
         return self                                                    # where any copies made above are freed in stream order
 
-    def __call__(self, persp):
+    gathers = True                  # f(persp, rows) reads the listed rows itself: _forward_chunked makes no copy of them
+
+    def __call__(self, persp, rows=None):
+        """``rows`` (int32 tensor on the device, any order, repeats allowed): the Q-values of ``persp[rows]`` -- the same
+        bits as ``f(persp)[rows]`` -- read from the stack in place (tq_nn11_forward_rows).  An index outside the stack
+        gives a Q-row of a zero perspective and makes check() raise."""
         persp, dtype = _check_stack(persp, self.system_size, self.device, "stack")
-        q = torch.empty((persp.shape[0], 3), dtype=torch.float32, device=self.device)
-        self._call(self._L.tq_nn11_forward, _ptr(persp), dtype, persp.shape[0], _ptr(q))
+        if rows is None:
+            q = torch.empty((persp.shape[0], 3), dtype=torch.float32, device=self.device)
+            self._call(self._L.tq_nn11_forward, _ptr(persp), dtype, persp.shape[0], _ptr(q))
+            return q
+        if rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != self.device:
+            raise ValueError(f"rows must be a 1-d int32 tensor on {self.device}, got {rows.dtype} {tuple(rows.shape)} on {rows.device}")
+        rows = rows.contiguous()
+        q = torch.empty((rows.shape[0], 3), dtype=torch.float32, device=self.device)
+        self._call(self._L.tq_nn11_forward_rows, _ptr(persp), dtype, persp.shape[0], _ptr(rows), rows.shape[0], _ptr(q))
         return q
 
     forward = __call__
+
+    def check(self):
+        """Reads and clears the device error latch (synchronises): ValueError for a row index outside the stack."""
+        self._call(self._L.tq_nn11_check)
 
     def eval(self):
         return self

@@ -37,7 +37,7 @@ def learnerStep(grad, target_model, memory, optimizer, batch_size, beta, discoun
     return loss, indices
 
 
-def _forward_chunked(model, persp, chunk, pad_to=1024, backing=None, out=None):
+def _forward_chunked(model, persp, chunk, pad_to=1024, backing=None, out=None, rows=None):
     """model(persp) in chunks of `chunk` rows -> (rows, 3) float32.  The number of perspectives changes every step, and
     every new batch size is a new problem for MIOpen's solver search, so the last, ragged chunk is run at a row count
     rounded up to a multiple of `pad_to` (its surplus Q rows are cut off again): a handful of shapes instead of
@@ -46,20 +46,28 @@ def _forward_chunked(model, persp, chunk, pad_to=1024, backing=None, out=None):
     zero-filled copy otherwise.  Batch rows do not influence each other, but a different row count may select a
     different convolution kernel and summation order: Q-values agree with the unpadded forward to ~1e-6, bit-identity
     needs ``pad_to=1`` (tests/test_gpu_policy.py pins both, and that the greedy choice is the same on the golden
-    weights).  ``out``: optional (>= rows, 3) float32 tensor to receive the Q-values (no torch.cat)."""
-    n = persp.shape[0]
+    weights).  ``out``: optional (>= rows, 3) float32 tensor to receive the Q-values (no torch.cat).
+    ``rows`` (int32 (R,) device tensor): model(persp[rows]) instead, the list walked in chunks -> (R, 3).  A model that
+    ``gathers`` (NN11Forward) reads the listed rows from ``persp`` in place; for any other, each chunk is
+    ``persp.index_select(0, rows)`` and then the model as before."""
+    n = persp.shape[0] if rows is None else rows.shape[0]
     if out is None:
         out = torch.empty((n, 3), dtype=torch.float32, device=persp.device)
+    gathers = rows is not None and getattr(model, "gathers", False)
     with torch.no_grad():
         for i in range(0, n, chunk):
-            x = persp[i:i + chunk]
+            if gathers:
+                part = rows[i:i + chunk]
+                out[i:i + part.shape[0]] = model(persp, part)
+                continue
+            x = persp[i:i + chunk] if rows is None else persp.index_select(0, rows[i:i + chunk].long())
             r = x.shape[0]
             if r < chunk and pad_to > 1 and r % pad_to and not getattr(model, "any_rows", False):
-                rows = min(chunk, (r + pad_to - 1) // pad_to * pad_to)
-                if backing is not None and backing.data_ptr() == persp.data_ptr() and backing.shape[0] >= i + rows:
-                    xp = backing[i:i + rows]
+                padded = min(chunk, (r + pad_to - 1) // pad_to * pad_to)
+                if rows is None and backing is not None and backing.data_ptr() == persp.data_ptr() and backing.shape[0] >= i + padded:
+                    xp = backing[i:i + padded]
                 else:
-                    xp = torch.zeros((rows,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
+                    xp = torch.zeros((padded,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
                     xp[:r] = x
                 out[i:i + r] = model(xp)[:r]
             else:
@@ -67,18 +75,26 @@ def _forward_chunked(model, persp, chunk, pad_to=1024, backing=None, out=None):
     return out[:n]
 
 
-def selectActionEnvSet(envs, model, epsilon, dtype=torch.float32, chunk=1 << 16):
+def selectActionEnvSet(envs, model, epsilon, dtype=torch.float32, chunk=1 << 16, sparse=False):
     """The reference's selectActionBatch for the lattices that live in ``envs`` (an EnvSet), everything
     on the device: perspectives -> model forward (in chunks) -> epsilon-greedy selection keyed by each
     lattice's own (episode, step) counters.
+    ``sparse``: the forward runs only on the perspectives the selection reads (EnvSet.selectPlan: one row of a lattice
+    that will not act greedily instead of all of its rows) -- the same actions and q_values in bits with a model whose
+    Q-row depends on nothing but the perspective (NN11Forward), for one more 8-byte read-back.
     -> (actions (N,4), q_values (N,3)); numpy with envs.numpy_io, device tensors otherwise."""
     model.eval()
     io = envs.numpy_io
     envs.numpy_io = False
     try:
         persp, pos, _ = envs.generatePerspectiveReused(dtype=dtype)       # consumed at once by the forward pass
-        q = _forward_chunked(model, persp, chunk, backing=envs.reusedStackBacking())
-        act, qv = envs.selectAction(q, epsilon, positions=pos)
+        if sparse:
+            plan = envs.selectPlan(epsilon)
+            q = _forward_chunked(model, persp, chunk, rows=plan.rows)
+            act, qv = envs.selectAction(q, epsilon, positions=pos, plan=plan)
+        else:
+            q = _forward_chunked(model, persp, chunk, backing=envs.reusedStackBacking())
+            act, qv = envs.selectAction(q, epsilon, positions=pos)
     finally:
         envs.numpy_io = io
     return envs._out(act, np.int64), envs._out(qv)
