@@ -527,6 +527,39 @@ int tq_nn11_grad_opt_step(tq_nn11_grad* h, int kind, double lr, double beta1, do
                           const float* const* grad_b, float* const* m_w, float* const* m_b, float* const* v_w,
                           float* const* v_b, void* stream);
 
+/* ---- The forward pass of the reference's two wide Q-networks on the device (src/nn/torch/NN.py:47-133), forward only:
+ *   TQ_NET_NN8   NN_8:  8 conv3x3 + ReLU, channels 2-256-256-240-224-220-215-205-200
+ *   TQ_NET_NN17  NN_17: 20 conv3x3 + ReLU despite its name, channels 2-256-256-251-250-240-240-235-233-233-229-225-223-
+ *                220-220-220-215-214-205-204-200
+ * each with NN_11's paddings (circular pad of 1 before the unpadded first conv, zero padding 1 in the middle convs, the
+ * last conv unpadded) and one linear layer from 200 * (d-2)^2 features to 3 outputs.  Same stacks in, same (P,3) f32
+ * Q-table out as tq_nn11_forward.  Their learner step and optimizer stay with the caller.  Design: DESIGN.md 3.10.
+ * Numerics contract -- NN_11's:
+ *  - conv and linear weights are rounded once to bf16 (round to nearest even) when they are loaded; all biases stay f32.
+ *  - a stack element is converted to bf16 (exact for the 0/1 the writer produces).
+ *  - each conv layer accumulates bf16 x bf16 products in f32 (MFMA), adds the f32 bias, applies ReLU in f32 and rounds to
+ *    bf16 (RNE) as the next layer's input; the last conv's output is rounded the same way.
+ *  - the linear layer accumulates in f32, adds the f32 bias and stores f32.
+ *  - channels are padded with zero weights and biases up to the MFMA granule (32), so a padded activation channel is 0.
+ *  - the order of every sum depends on (net, layer, d) alone; no atomics: the same call gives the same bits, and a row's
+ *    bits do not depend on its place in the batch or on how the call is cut into passes.
+ * One handle, one stream, as for tq_nn11_*: create / destroy allocate and synchronise, load and forward only enqueue. */
+#define TQ_NET_NN8 8
+#define TQ_NET_NN17 17
+typedef struct tq_nnw tq_nnw;
+/* NN_8 / NN_17(system_size = d, number_of_actions = 3) for passes of up to max_rows perspectives: allocates the packed
+ * weights and two activation images of max_rows * d*d * 256 bf16.  Checked before the device is touched: out NULL, net
+ * neither, d even or unsupported, max_rows outside 1..2^24 -> TQ_E_INVALID. */
+int tq_nnw_create(tq_nnw** out, int net, int d, int64_t max_rows, int device);
+int tq_nnw_destroy(tq_nnw* h);
+/* model.load_state_dict: weights[L + 1] / biases[L + 1] (L = 8 or 20 conv layers) are HOST arrays of device pointers to
+ * f32 tensors in torch layout -- conv1..convL weight [cout][cin][3][3] and bias [cout], then linear1 weight
+ * [3][200*(d-2)^2] (features in (channel, y, x) order) and bias [3].  Packs on the device. */
+int tq_nnw_load(tq_nnw* h, const float* const* weights, const float* const* biases, void* stream);
+/* model(stack): stack[rows][2][d][d] of element type dtype (TQ_F32 / TQ_F16 / TQ_BF16 / TQ_U8, 16-byte aligned) -> q
+ * f32[rows][3].  Any rows >= 0: the call walks passes of max_rows itself.  TQ_E_INVALID before the first tq_nnw_load. */
+int tq_nnw_forward(tq_nnw* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -747,3 +747,4 @@ int tq_check(tq_env* h, void* stream_) {
 #include "abi_nn11.hpp"
 #include "abi_nn11_grad.hpp"
 #include "abi_nn11_opt.hpp"
+#include "abi_nnw.hpp"
