@@ -560,6 +560,57 @@ int tq_nnw_load(tq_nnw* h, const float* const* weights, const float* const* bias
  * f32[rows][3].  Any rows >= 0: the call walks passes of max_rows itself.  TQ_E_INVALID before the first tq_nnw_load. */
 int tq_nnw_forward(tq_nnw* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
 
+/* ---- The forward pass of the reference's BasicBlock ResNets on the device (src/nn/torch/ResNet.py), forward only and
+ * with BatchNorm in inference form only (running statistics: the network as model.eval() computes it):
+ *   TQ_NET_RESNET18  ResNet(BasicBlock, [2,2,2,2]), the reference launcher's default model
+ *   TQ_NET_RESNET34  ResNet(BasicBlock, [3,4,6,3]): the same layer shapes, other block counts
+ * conv1 3x3 2 -> 64 (zero padding 1, no bias) + bn1 + ReLU; layer1..layer4 of BasicBlocks at 64 / 128 / 256 / 512
+ * channels, relu(bn2(conv2(relu(bn1(conv1(x))))) + shortcut(x)), the shortcut being the identity or, in the first block of
+ * layer2..layer4, conv1x1 + bn; layer4's first block has stride 2, so for lattice size d the pixel grid is d x d up to
+ * layer3 and s x s, s = (d+1)/2, from there on: the 3x3 of stride 2 reads source pixel (2y+ky-1, 2x+kx-1), zero outside
+ * the grid, the 1x1 of stride 2 reads (2y, 2x); then the average over the s^2 pixels and Linear(512, 3).  Same stacks in,
+ * same (P,3) f32 Q-table out as tq_nn11_forward.  A training-mode forward (batch statistics), the learner step and the
+ * optimizer stay with the caller.  Design: DESIGN.md 3.11.
+ * Numerics contract -- NN_11's extended.  All arithmetic is f32, every operation rounded once, nothing contracted; sqrt and
+ * / are IEEE correctly rounded:
+ *  - a stack element is converted to bf16 (exact for 0/1); conv weights are rounded once to bf16 (RNE), unscaled, when
+ *    they are loaded; every convolution is a sum of bf16 x bf16 products in f32 (MFMA).
+ *  - BatchNorm is folded at load into two f32 vectors per convolution: scale s = gamma / sqrt(running_var + eps), shift
+ *    t = beta - running_mean * s (eps as f32); padding channels get s = 0 and t = 0, so a padded activation channel is 0.
+ *  - epilogue of a convolution: z = acc * s + t; for a block's second convolution z = z + r, r being the f32 value of the
+ *    shortcut's bf16 element (the block's input image, or the shortcut convolution's image); then ReLU; then ONE rounding
+ *    to bf16 (RNE).
+ *  - a shortcut convolution writes bf16(acc * s + t), without ReLU.  This rounding point has no counterpart in torch,
+ *    where the shortcut's f32 value is added unrounded.
+ *  - head: S[c] is the f32 sum of channel c over the s^2 pixels in pixel order; Q[a] = (sum_c S[c] * bf16(W[a][c])) / s^2
+ *    + b[a], the sum over c in a fixed order (a lane's eight channels in order, then a butterfly over the 64 lanes).
+ *    Dividing after the linear sum is mathematically torch's mean-then-linear and keeps every intermediate an integer on
+ *    integer networks, so the head is exact there at every size, not only where s^2 is a power of two.
+ *  - the order of every sum is (chunk, tap, k-step) and depends on (net, convolution, d) alone; no atomics: the same call
+ *    gives the same bits, and a row's bits do not depend on its place in the batch, on the row count or on how the call is
+ *    cut into passes.
+ * One handle, one stream, as for tq_nn11_*: create / destroy allocate and synchronise, load and forward only enqueue. */
+#define TQ_NET_RESNET18 18
+#define TQ_NET_RESNET34 34
+typedef struct tq_resnet tq_resnet;
+/* ResNet18 / ResNet34 at lattice size d for passes of up to max_rows perspectives: allocates the packed weights and four
+ * activation images of max_rows * d*d * 256 bf16 (a block's input, mid image, shortcut image and output are live at once;
+ * 512 s^2 <= 256 d^2 for every supported d).  The weights do not depend on d.  Checked before the device is touched: out
+ * NULL, net neither, d even or unsupported, max_rows outside 1..2^24 -> TQ_E_INVALID. */
+int tq_resnet_create(tq_resnet** out, int net, int d, int64_t max_rows, int device);
+int tq_resnet_destroy(tq_resnet* h);
+/* model.load_state_dict: conv_weights[n] and bn_params[4 n] (n = 20 or 36 convolutions) are HOST arrays of device
+ * pointers to f32 tensors in torch layout, in the order of the module's state_dict -- conv1, then per block conv1, conv2
+ * and, where the block has one, shortcut.0: weight [cout][cin][3][3] or [cout][cin][1][1]; bn_params[4 i ..] are
+ * convolution i's BatchNorm weight (gamma), bias (beta), running_mean and running_var, [cout] each.  lin_w: linear.weight
+ * [3][512], lin_b: linear.bias [3], device pointers.  eps: the BatchNorm layers' eps, > 0.  Packs and folds on the device. */
+int tq_resnet_load(tq_resnet* h, const float* const* conv_weights, const float* const* bn_params, const float* lin_w,
+                   const float* lin_b, double eps, void* stream);
+/* model.eval()(stack): stack[rows][2][d][d] of element type dtype (TQ_F32 / TQ_F16 / TQ_BF16 / TQ_U8, 16-byte aligned) ->
+ * q f32[rows][3].  Any rows >= 0: the call walks passes of max_rows itself.  TQ_E_INVALID before the first
+ * tq_resnet_load. */
+int tq_resnet_forward(tq_resnet* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

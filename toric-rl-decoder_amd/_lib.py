@@ -19,6 +19,7 @@ TQ_F32, TQ_F16, TQ_BF16, TQ_U8 = 0, 1, 2, 3
 TQ_PERR_FIXED, TQ_PERR_LINEAR, TQ_PERR_RANDOM = 0, 1, 2
 TQ_OPT_ADAM, TQ_OPT_RMSPROP = 0, 1
 TQ_NET_NN8, TQ_NET_NN17 = 8, 17
+TQ_NET_RESNET18, TQ_NET_RESNET34 = 18, 34
 TQ_E_INVALID, TQ_E_HIP, TQ_E_CAPACITY, TQ_E_ACTION, TQ_E_INDEX, TQ_E_RESET = -1, -2, -3, -4, -5, -6
 
 # every symbol include/toricenv.h declares: (name, restype, argtypes)
@@ -104,6 +105,10 @@ SYMBOLS = [
     ("tq_nnw_destroy", _i, [_vp]),
     ("tq_nnw_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     ("tq_nnw_forward", _i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    ("tq_resnet_create", _i, [C.POINTER(_vp), _i, _i, _i64, _i]),
+    ("tq_resnet_destroy", _i, [_vp]),
+    ("tq_resnet_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _d, _vp]),
+    ("tq_resnet_forward", _i, [_vp, _vp, _i, _i64, _vp, _vp]),
 ]
 
 _lib = None

@@ -748,3 +748,4 @@ int tq_check(tq_env* h, void* stream_) {
 #include "abi_nn11_grad.hpp"
 #include "abi_nn11_opt.hpp"
 #include "abi_nnw.hpp"
+#include "abi_resnet.hpp"

@@ -4,7 +4,8 @@ The Q-network NN_11 (nn11.py: the torch module, same parameter names as the refe
 unchanged, and its HIP counterparts NN11Forward / NN11Grad / NN11Optimizer) is imported here, so that BASELINE
 configs[2] ("generatePerspective feeding NN_11 policy for selectAction") and the evaluation loop can run without the
 reference's Python.  An NN11Forward is accepted wherever a ``model`` is, and so is an NNWideForward (nnw.py: the
-reference's NN_8 and NN_17, forward only).
+reference's NN_8 and NN_17, forward only) and a ResNetForward (resnet.py: the launcher's default ResNet18, and ResNet34,
+eval-mode forward only).
 
   selectActionBatch    src/numba/util_actor.py:11-53
   predictMaxOptimized  src/util_learner.py:48-111
@@ -20,6 +21,7 @@ from ._lib import _ptr, _stream, check, to_device
 from .envset import EnvSet, ToricEnv, generatePerspectiveBatch
 from .nn11 import NN_11, NN11Forward, NN11Grad, NN11Optimizer  # noqa: F401  (their callers import them from here)
 from .nnw import NN_8, NN_17, NNWideForward  # noqa: F401  (the wide nets, forward only: nnw.py)
+from .resnet import ResNet18, ResNet34, ResNetForward  # noqa: F401  (the BasicBlock ResNets, eval-mode forward only: resnet.py)
 
 
 def learnerStep(grad, target_model, memory, optimizer, batch_size, beta, discount=0.95, batch=None):
