@@ -107,8 +107,8 @@ int tq_stack_free(void* ptr);
 
 /* The stack write runs one persistent workgroup per CU, each with a fixed contiguous share of the stack, dealt to the
  * XCDs round-robin.  On MI355X the CUs of the odd XCDs store this stream ~20 % slower than those of the even ones (every
- * box and buffer measured: profiles/r04_workgroup_end_times.txt), so of every pair of workgroups the even one takes
- * 32 + bias and the odd one 32 - bias of the pair's 64 fine parts -- for d >= 7, f32 / f16 / bf16 stacks of 64 MB and more
+ * box and buffer measured: profiles/r04_workgroup_end_times.txt), so of every pair of neighbouring workgroups the one on
+ * an even XCD takes 32 + bias and the other one 32 - bias of the pair's 64 fine parts -- for d >= 7, f32 / f16 / bf16 stacks of 64 MB and more
  * (smaller lattices and the u8 stack are bound by the producers, not by the stores: there unequal shares only cost).  Default 5 (or the
  * environment variable TORICENV_XCD_BIAS, read once); 0 = equal shares; changes the speed of tq_persp_write*, never
  * its result.  tq_set_xcd_bias is the process-wide setting, tq_env_set_xcd_bias one handle's own (-1 = follow the
@@ -118,6 +118,14 @@ int tq_set_xcd_bias(int bias);   /* 0..16, else TQ_E_INVALID */
 int tq_get_xcd_bias(void);
 int tq_env_set_xcd_bias(tq_env* h, int bias);   /* -1..16 */
 int tq_env_get_xcd_bias(const tq_env* h);       /* the setting in force for this handle */
+/* Test hooks of the unequal shares.  A pair's two workgroups settle who takes the larger share over one word of device
+ * memory, by the parity of the XCD each runs on; on a round-robin dispatcher the two always differ.
+ * tq_debug_force_xcc_parity (process-wide): -1 = the hardware's answer (the default), 0 / 1 = every workgroup claims that
+ * parity (so both of a pair prefer the same share), 2 = the parity read, inverted.  Never changes what is written.
+ * tq_debug_slot_words_nonzero: waits for the device, then counts the words of the handle's eight sets that are not zero --
+ * every write leaves them zero (< 0: an error code). */
+int tq_debug_force_xcc_parity(int parity);      /* -1..2, else TQ_E_INVALID */
+int tq_debug_slot_words_nonzero(tq_env* h);
 
 int tq_num_envs(const tq_env* h);
 int tq_size(const tq_env* h);
@@ -165,7 +173,7 @@ int tq_persp_count(tq_env* h, int32_t* counts, int64_t* offsets, void* stream);
  * batch) are refused -- the kernel stores nothing outside [0, min(offsets[N], capacity)) perspectives, every wait in
  * it is bounded, the grid drains, and TQ_E_INVALID is latched for tq_check; the handle stays usable.
  * At most EIGHT stack writes of one handle may be in flight at a time (on whatever streams): their workgroups take their
- * shares through a ring of eight counter sets (tq_set_xcd_bias); a write captured into a HIP graph may be replayed. */
+ * shares through a ring of eight sets of words (tq_set_xcd_bias); a write captured into a HIP graph may be replayed. */
 int tq_persp_write(tq_env* h, const int64_t* offsets, void* out, int32_t* positions,
                    int64_t capacity, int dtype, void* stream);
 /* The same for the lattices [first, first + count) only: `out` / `positions` receive the perspectives

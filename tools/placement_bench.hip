@@ -20,7 +20,7 @@
 #include <random>
 #include <vector>
 
-#include "stream_write.hpp"   // (the kernel is called with its 257-entry table: equal shares (lg = 8, bias 0, no slot counters), as when this harness was written)
+#include "stream_write.hpp"   // (the kernel is called with its 257-entry table: equal shares (lg = 8, bias 0, no pair words), as when this harness was written)
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s (line %d)\n", #x, hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
@@ -119,7 +119,7 @@ int main(int argc, char** argv) {
         for (int r = 0; r <= reps; ++r) {
             CK(hipEventRecord(e0));
             hipLaunchKernelGGL((tq::k_persp_stream<D, float, 4, 11, 8, 14, 12>), dim3(256), dim3(1024), 0, 0, vp, N, (const int64_t*)off, out, pos, P, err,
-                               (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, (unsigned long long*)nullptr);
+                               (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, -1, (unsigned long long*)nullptr);
             CK(hipGetLastError());
             CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1));
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));

@@ -5,6 +5,9 @@
 // (STATS instantiation) of chosen configurations.  Build here, run on the GPU box:
 //   hipcc -O3 -std=c++17 -ffp-contract=off --offload-arch=gfx950 -Iinclude -Itoric-rl-decoder_amd/csrc tools/stream_tune.hip -o tools/stream_tune
 //   tools/stream_tune <d> <dtype: f32|bf16|u8> [lattices=65536]
+// TUNE_START=1: the start of a launch by the kernel's own clock (STATS instantiation, bias TUNE_START_BIAS or 5, the best buffer),
+// three launches read.  Built with -DTUNE_OTHER_HPP='"file.hpp"' -- another version of stream_write.hpp whose namespace is tqo { using
+// namespace tq; ... } and whose kernel takes the same arguments -- the two kernels run in turn and the table holds both.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -17,6 +20,9 @@
 
 #include "stream_write.hpp"
 #include "stream_write_runs.hpp"
+#ifdef TUNE_OTHER_HPP
+#include TUNE_OTHER_HPP
+#endif
 
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { printf("%s: %s (line %d)\n", #x, hipGetErrorString(e_), __LINE__); exit(1); } } while (0)
 
@@ -73,6 +79,8 @@ struct Timer {
     }
 };
 
+constexpr int SLOT_SET = tq::pair_set_words(512);            // the pair words of one launch of up to 512 workgroups
+
 struct Ctx {
     const uint64_t* vp; int64_t N; const int64_t* off; void* out; int32_t* pos; int64_t P; int* err; const int32_t* split;
     void* ref; int32_t* pref; unsigned long long* bad; double bytes; size_t out_bytes; Timer* t;
@@ -88,7 +96,7 @@ void launch_kind(Ctx& c, int grid, const int32_t* sp, unsigned long long* st) {
     if constexpr (KIND == 2) {
         hipLaunchKernelGGL((tq::k_persp_stream<D, OutT, NS, NP, CPW, RB, RP, STATS, NPW>), dim3(grid), dim3(64 * WV), 0, 0, c.vp, c.N, c.off,
                            (OutT*)c.out, c.pos, c.P, c.err, (int64_t)0, c.N, sp ? c.split_fine : nullptr, grid == 256 ? 13 : 14, c.bias,
-                           c.ticket + 8 + tq::STREAM_SLOT_WORDS * (c.launches % 8), st);
+                           c.ticket + 8 + SLOT_SET * (c.launches % 8), -1, st);
         ++c.launches;
     } else if constexpr (KIND == 1) {
         hipLaunchKernelGGL((tqr::k_persp_stream<D, OutT, NS, NP, CPW, RB, RP, STATS, NPW, SCHED>), dim3(grid), dim3(64 * WV), 0, 0, c.vp, c.N, c.off,
@@ -198,6 +206,73 @@ void one(Ctx& c, bool stats, bool is_ref) {
     CK(hipFree(st));
 }
 
+// The start of a launch by the kernel's own clock: means over the 256 workgroups, us after the workgroup began, of producer
+// 0's stamps (range known, first lattice loaded, first lattice in the ring) and of the storers' first trip (min / mean / max).
+struct StartStamps { double known = 0, loaded = 0, ring = 0, trip_min = 1e9, trip_mean = 0, trip_max = 0; };
+template <int NS, int NPW, int NP>
+StartStamps start_stamps(const std::vector<unsigned long long>& h) {
+    constexpr int WV = NS + NPW + NP;
+    StartStamps s; int n = 0, nt = 0;
+    for (int g = 0; g < 256; ++g) {
+        const unsigned long long x = h[((size_t)g * WV + NS + NPW) * 4 + 3] >> 16;
+        if (x >> 32) { s.known += (double)(x & 0xFFFF) / 100.0; s.loaded += (double)((x >> 16) & 0xFFFF) / 100.0; s.ring += (double)((x >> 32) & 0xFFFF) / 100.0; ++n; }
+        double f = 1e9;
+        for (int w = 0; w < NS; ++w) { const unsigned long long t = h[((size_t)g * WV + w) * 4 + 3] >> 16; if (t) f = std::min(f, (double)t / 100.0); }
+        if (f < 1e9) { s.trip_min = std::min(s.trip_min, f); s.trip_max = std::max(s.trip_max, f); s.trip_mean += f; ++nt; }
+    }
+    if (n) { s.known /= n; s.loaded /= n; s.ring /= n; }
+    if (nt) s.trip_mean /= nt;
+    return s;
+}
+template <int D, typename OutT, int NS, int NPW, int NP>
+void start_table(Ctx& c) {
+    constexpr int WV = NS + NPW + NP;
+    unsigned long long* st;
+    CK(hipMalloc(&st, sizeof(unsigned long long) * 256 * WV * 4));
+    std::vector<unsigned long long> h((size_t)256 * WV * 4);
+    auto launch = [&](int which) {
+        CK(hipMemset(st, 0, sizeof(unsigned long long) * 256 * WV * 4));
+        unsigned int* words = c.ticket + 8 + SLOT_SET * (c.launches++ % 8);
+        if (which == 0)
+            hipLaunchKernelGGL((tq::k_persp_stream<D, OutT, NS, NP, 8, 14, 12, true, NPW>), dim3(256), dim3(64 * WV), 0, 0, c.vp, c.N, c.off, (OutT*)c.out, c.pos, c.P,
+                               c.err, (int64_t)0, c.N, c.split_fine, 13, c.bias, words, -1, st);
+#ifdef TUNE_OTHER_HPP
+        else
+            hipLaunchKernelGGL((tqo::k_persp_stream<D, OutT, NS, NP, 8, 14, 12, true, NPW>), dim3(256), dim3(64 * WV), 0, 0, c.vp, c.N, c.off, (OutT*)c.out, c.pos, c.P,
+                               c.err, (int64_t)0, c.N, c.split_fine, 13, c.bias, words, -1, st);
+#endif
+        CK(hipGetLastError()); CK(hipDeviceSynchronize());
+        CK(hipMemcpy(h.data(), st, h.size() * 8, hipMemcpyDeviceToHost));
+    };
+#ifdef TUNE_OTHER_HPP
+    const int kernels = 2;
+#else
+    const int kernels = 1;
+#endif
+    const char* name[2] = {"this kernel ", "other kernel"};
+    for (int r = 0; r < 3; ++r) for (int k = kernels - 1; k >= 0; --k) launch(k);     // warm code
+    double trip[2][3];
+    printf(" the start of a launch, bias %d: means over 256 workgroups, us after the workgroup began\n", c.bias);
+    for (int r = 0; r < 3; ++r)
+        for (int k = kernels - 1; k >= 0; --k) {
+            launch(k);
+            const StartStamps s = start_stamps<NS, NPW, NP>(h);
+            trip[k][r] = s.trip_mean;
+            printf("   %s reading %d: range known %5.2f  first lattice loaded %5.2f  in the ring %5.2f  first storer trip min %5.2f mean %5.2f max %5.2f\n",
+                   name[k], r, s.known, s.loaded, s.ring, s.trip_min, s.trip_mean, s.trip_max);
+        }
+    int e; CK(hipMemcpy(&e, c.err, 4, hipMemcpyDeviceToHost));
+    std::vector<unsigned int> words(8 * SLOT_SET);
+    CK(hipMemcpy(words.data(), c.ticket + 8, words.size() * 4, hipMemcpyDeviceToHost));
+    int nz = 0; for (unsigned int x : words) nz += x != 0u;
+    for (int k = kernels - 1; k >= 0; --k) {
+        const double mn = std::min({trip[k][0], trip[k][1], trip[k][2]}), mx = std::max({trip[k][0], trip[k][1], trip[k][2]});
+        printf("   %s first trip, mean of the three readings %5.2f us, spread %4.2f us\n", name[k], (trip[k][0] + trip[k][1] + trip[k][2]) / 3, mx - mn);
+    }
+    printf("   latch %d, pair words not zero afterwards: %d\n", e, nz);
+    CK(hipFree(st));
+}
+
 // Would a split of the stack that follows the workgroups' OBSERVED rates end the launch sooner?  Pass 0: the scan's equal
 // split, the workgroups' end times from the STATS instantiation; pass k: cut points such that workgroup g gets a share
 // proportional to share_g / end_g of the pass before.  (What a dynamic hand-out of parts would converge to.)
@@ -219,13 +294,13 @@ void rebalance(Ctx& c, const std::vector<int64_t>& off_h) {
         cut[0] = 0; cut[256] = (int32_t)N;
         CK(hipMemcpy(sp, cut.data(), 4 * 257, hipMemcpyHostToDevice));
         auto k = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, OutT, NS, NP, 8, 14, 12, false, NPW>), dim3(256), dim3(64 * WV), 0, 0, c.vp, c.N, c.off,
-                                          (OutT*)c.out, c.pos, c.P, c.err, (int64_t)0, c.N, (const int32_t*)sp, 8, 0, (unsigned int*)nullptr, (unsigned long long*)nullptr); };
+                                          (OutT*)c.out, c.pos, c.P, c.err, (int64_t)0, c.N, (const int32_t*)sp, 8, 0, (unsigned int*)nullptr, -1, (unsigned long long*)nullptr); };
         float a = 0, mn = 1e9;
         for (int r = 0; r < 9; ++r) { float x = c.t->run(k); if (r) { a += x; mn = std::min(mn, x); } }
         for (int r = 0; r < 3; ++r) {
             CK(hipMemset(st, 0, sizeof(unsigned long long) * 256 * WV * 4));
             hipLaunchKernelGGL((tq::k_persp_stream<D, OutT, NS, NP, 8, 14, 12, true, NPW>), dim3(256), dim3(64 * WV), 0, 0, c.vp, c.N, c.off, (OutT*)c.out, c.pos, c.P,
-                               c.err, (int64_t)0, c.N, (const int32_t*)sp, 8, 0, (unsigned int*)nullptr, st);
+                               c.err, (int64_t)0, c.N, (const int32_t*)sp, 8, 0, (unsigned int*)nullptr, -1, st);
             CK(hipDeviceSynchronize());
         }
         std::vector<unsigned long long> h((size_t)256 * WV * 4);
@@ -280,7 +355,7 @@ int run(int64_t N, double q, const char* tname) {
                            (const int64_t*)part, off, (int32_t*)nullptr, N, sf, tqr::STREAM_DYN_LG);
         CK(hipDeviceSynchronize());
         c.split_fine = sf;
-        CK(hipMalloc(&c.ticket, 4 * (8 + 8 * tq::STREAM_SLOT_WORDS))); CK(hipMemset(c.ticket, 0, 4 * (8 + 8 * tq::STREAM_SLOT_WORDS)));   // 8 ticket counters (runs experiment) + 8 sets of slot counters
+        CK(hipMalloc(&c.ticket, 4 * (8 + 8 * SLOT_SET))); CK(hipMemset(c.ticket, 0, 4 * (8 + 8 * SLOT_SET)));   // 8 ticket counters (runs experiment) + 8 sets of pair words
     }
     CK(hipMalloc(&c.ref, out_bytes)); CK(hipMalloc(&c.pref, (size_t)P * 12 + 4096)); CK(hipMalloc(&c.pos, (size_t)P * 12 + 4096)); CK(hipMalloc(&c.bad, 8));
     // candidate buffers: the product configuration on each, the fastest is used for the sweep
@@ -297,13 +372,19 @@ int run(int64_t N, double q, const char* tname) {
     for (int b = 0; b < 8; ++b) {
         void* ob = bufs[b];
         auto k = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, OutT, NS0, NP0, 8, 14, 12>), dim3(256), dim3(64 * (NS0 + 1 + NP0)), 0, 0, vp, N, off, (OutT*)ob, c.pos, P, err,
-                                          (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, (unsigned long long*)nullptr); };
+                                          (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, -1, (unsigned long long*)nullptr); };
         float a = 0; for (int r = 0; r < 6; ++r) { float x = t.run(k); if (r) a += x; }
         printf(" %s %.0f", b < 2 ? "hipMalloc" : "vmm", bytes / (a / 5) / 1e6);
         if (a < best_ms) { best_ms = a; best = b; }
     }
     printf("  -> buffer %d\n", best);
     c.out = bufs[best];
+    if (getenv("TUNE_START")) {
+        constexpr int NPW0 = (ES < 4 && D >= 5) ? 2 : 1, NSP = D == 5 && ES == 2 ? 3 : NS0, NPP = D >= 17 ? 3 : (D >= 13 ? 8 - NPW0 : 16 - NSP - NPW0);
+        c.bias = getenv("TUNE_START_BIAS") ? atoi(getenv("TUNE_START_BIAS")) : 5;     // (0: equal shares, no atomic)
+        start_table<D, OutT, NSP, NPW0, NPP>(c);
+        return 0;
+    }
     if (getenv("TUNE_BIAS")) {                                // unequal fixed shares for even / odd XCDs, on every buffer
         constexpr int NPW0 = (ES < 4 && D >= 5) ? 2 : 1, NSP = D == 5 && ES == 2 ? 3 : NS0, NPP = D >= 17 ? 3 : (D >= 13 ? 8 - NPW0 : 16 - NSP - NPW0);
         const bool st = getenv("TUNE_STATS") != nullptr;
@@ -410,9 +491,9 @@ int run_all(int64_t N, double q) {
         void* ob;
         if (b < 2) CK(hipMalloc(&ob, out_bytes + (size_t)b * (3u << 20)));
         else ob = alloc_vmm(out_bytes + (size_t)b * (2u << 20));
-        auto kf = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, float, NS0, NP1, 8, 14, 12, false, 1>), dim3(256), dim3(64 * (NS0 + 1 + NP1)), 0, 0, vp, N, off, (float*)ob, pos, P, err, (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, (unsigned long long*)nullptr); };
-        auto kb = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, tq::bf16_t, NS0, NP2, 8, 14, 12, false, 2>), dim3(256), dim3(64 * (NS0 + 2 + NP2)), 0, 0, vp, N, off, (tq::bf16_t*)ob, pos, P, err, (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, (unsigned long long*)nullptr); };
-        auto ku = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, uint8_t, NS0, NP2, 8, 14, 12, false, 2>), dim3(256), dim3(64 * (NS0 + 2 + NP2)), 0, 0, vp, N, off, (uint8_t*)ob, pos, P, err, (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, (unsigned long long*)nullptr); };
+        auto kf = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, float, NS0, NP1, 8, 14, 12, false, 1>), dim3(256), dim3(64 * (NS0 + 1 + NP1)), 0, 0, vp, N, off, (float*)ob, pos, P, err, (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, -1, (unsigned long long*)nullptr); };
+        auto kb = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, tq::bf16_t, NS0, NP2, 8, 14, 12, false, 2>), dim3(256), dim3(64 * (NS0 + 2 + NP2)), 0, 0, vp, N, off, (tq::bf16_t*)ob, pos, P, err, (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, -1, (unsigned long long*)nullptr); };
+        auto ku = [&] { hipLaunchKernelGGL((tq::k_persp_stream<D, uint8_t, NS0, NP2, 8, 14, 12, false, 2>), dim3(256), dim3(64 * (NS0 + 2 + NP2)), 0, 0, vp, N, off, (uint8_t*)ob, pos, P, err, (int64_t)0, N, (const int32_t*)split, 8, 0, (unsigned int*)nullptr, -1, (unsigned long long*)nullptr); };
         auto km4 = [&] { (void)hipMemsetAsync(ob, 1, (size_t)P * NQ * 4, 0); };
         auto km2 = [&] { (void)hipMemsetAsync(ob, 1, (size_t)P * NQ * 2, 0); };
         auto km1 = [&] { (void)hipMemsetAsync(ob, 1, (size_t)P * NQ, 0); };

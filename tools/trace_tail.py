@@ -19,3 +19,9 @@ print(f"dispatches in the trace: {len(dur)}; all: mean {statistics.mean(dur) / 1
 tail = dur[-(steps + after):-after] if after else dur[-steps:]
 print(f"timed region (the last {steps} before the final {after}): mean {statistics.mean(tail) / 1e3:.2f} us, median {statistics.median(tail) / 1e3:.2f}, "
       f"min {min(tail) / 1e3:.2f}, max {max(tail) / 1e3:.2f}, first {tail[0] / 1e3:.2f}")
+# gap = start of a write minus the end of the write before it (the write's stream carries nothing else in the timed region)
+span = rows[-(steps + after):-after] if after else rows[-steps:]
+gaps = [b[0] - (a[0] + a[1]) for a, b in zip(span, span[1:])]
+if gaps:
+    print(f"gap in front of a write: mean {statistics.mean(gaps) / 1e3:.2f} us, median {statistics.median(gaps) / 1e3:.2f}, min {min(gaps) / 1e3:.2f}; "
+          f"period {(span[-1][0] - span[0][0]) / (len(span) - 1) / 1e3:.2f} us")

@@ -38,6 +38,8 @@ SYMBOLS = [
     ("tq_get_xcd_bias", _i, []),
     ("tq_env_set_xcd_bias", _i, [_vp, _i]),
     ("tq_env_get_xcd_bias", _i, [_vp]),
+    ("tq_debug_force_xcc_parity", _i, [_i]),
+    ("tq_debug_slot_words_nonzero", _i, [_vp]),
     ("tq_num_envs", _i, [_vp]),
     ("tq_size", _i, [_vp]),
     ("tq_reset_all", _i, [_vp, _vp, _vp]),

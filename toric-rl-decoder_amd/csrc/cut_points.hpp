@@ -60,10 +60,14 @@ TQ_HD void cut_header_store(int32_t* split, int LG, int64_t total, int64_t N) {
     int32_t* h = split + (1 << LG) + 1;
     h[0] = (int32_t)(uint32_t)total; h[1] = (int32_t)(uint32_t)((uint64_t)total >> 32); h[2] = (int32_t)N;
 }
+TQ_HD constexpr int cut_header_at(int LG) { return (1 << LG) + 1; }                          // index of the header's first word
+TQ_HD bool cut_header_words_match(int32_t h0, int32_t h1, int32_t h2, int64_t p_tab, int64_t e_begin, int64_t e_end) {
+    const int64_t t_all = (int64_t)(((uint64_t)(uint32_t)h1 << 32) | (uint32_t)h0);
+    return t_all == p_tab && e_begin == 0 && (int64_t)h2 == e_end;
+}
 TQ_HD bool cut_header_matches(const int32_t* split, int LG, int64_t p_tab, int64_t e_begin, int64_t e_end) {
-    const int32_t* h = split + (1 << LG) + 1;
-    const int64_t t_all = (int64_t)(((uint64_t)(uint32_t)h[1] << 32) | (uint32_t)h[0]);
-    return t_all == p_tab && e_begin == 0 && (int64_t)h[2] == e_end;
+    const int32_t* h = split + cut_header_at(LG);
+    return cut_header_words_match(h[0], h[1], h[2], p_tab, e_begin, e_end);
 }
 
 }  // namespace tq

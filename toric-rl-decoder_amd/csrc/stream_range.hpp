@@ -13,6 +13,26 @@ TQ_HD void slot_fine_parts(int large, int idx, int RR, int bias, int& f_lo, int&
     f_hi = f_lo + (large ? RR + bias : RR - bias);
 }
 
+// Which of its pair's two slots a workgroup takes.  Workgroups b and b ^ 1 share pair b >> 1 and one word, zero between
+// launches; each adds pair_claim(0, prefers_large).add to it once (a returning atomic) and reads its kind from what the
+// word held before: 0 = it is the first of the pair and takes the kind it prefers; 1 / 3 = the other one came first and
+// took the small / large slot, this one takes what is left (its own preference if the two differ) and stores 0 to the
+// word again.  Anything else (kind = -1) is a word that no launch leaves behind: refused.
+constexpr int PAIR_WORD_STRIDE = 32;                          // dwords: every pair's word on a 128-byte line of its own
+TQ_HD constexpr int pair_set_words(int workgroups) { return workgroups / 2 * PAIR_WORD_STRIDE; }    // words of one launch
+struct PairClaim {
+    unsigned add;                     // what this workgroup adds to the pair's word
+    int kind;                         // 1 = the large slot, 0 = the small one, -1 = refused
+    bool second;                      // the second of the pair: it leaves the word zero
+};
+TQ_HD PairClaim pair_claim(unsigned old, int prefers_large) {
+    PairClaim c;
+    c.add = 1u + 2u * (unsigned)(prefers_large != 0);
+    c.second = old != 0u;
+    c.kind = old == 0u ? (prefers_large != 0) : (old == 1u ? 1 : (old == 3u ? 0 : -1));
+    return c;
+}
+
 // One workgroup's part of the output.  It produces the perspectives [Q0, Q1) of a stack of p_all (NQ elements of `esize`
 // bytes and 3 position dwords each) and stores the 128-byte lines whose FIRST element lies in that range, whole: the
 // leading elements of the line that holds its first element are left to the range before, and for the trailing elements

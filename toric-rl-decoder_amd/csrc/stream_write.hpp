@@ -21,7 +21,7 @@
 // range: its producers simply go on for the few perspectives that line needs (`need_extra`).  That arithmetic, the
 // slot -> fine parts mapping is stream_range.hpp, the cut points are cut_points.hpp: host + device, tested without a GPU.
 //
-// The kernel, in the order of this file: stream_setup (workgroup-uniform: slot, cut points, capacity, range), one function
+// The kernel, in the order of this file: stream_setup (workgroup-uniform: the pair's slot, cut points, capacity, range), one function
 // per role -- storer_wave, positions_wave, producer_wave -- and the entry k_persp_stream, which runs the set-up and
 // dispatches on the wave number.  The roles share StreamShape, StreamCtx, wait_until and StreamStats.
 #pragma once
@@ -31,7 +31,6 @@
 namespace tq {
 
 constexpr int ERR_INTERNAL = 32;
-constexpr int STREAM_SLOT_WORDS = 4;                           // slot counters of one launch of k_persp_stream: large, small, done (+ 1 pad)
 constexpr int STREAM_SPIN_LIMIT = 1 << 21;
 
 // Hand-off words live in LDS, which one workgroup's waves see coherently, and a wave's LDS operations execute in
@@ -228,81 +227,107 @@ __device__ __forceinline__ uint32_t produced(const uint32_t* pq, int lane) {
 // ---- the workgroup's range (uniform over the workgroup; false = nothing to do, or refused and latched: every wave
 // returns).  Also clears the rings and the hand-off words.  The stack is cut into 1 << lg FINE parts of equal perspective
 // count, RR of them per workgroup on average (a power of two): cut points from the scan's table `split` (k_scan_final),
-// or -- split == nullptr: a lattice sub-range, or offsets that did not come with the scan -- found here by waves 0 and 1.
+// or -- no table of these offsets: a lattice sub-range, or offsets that did not come with the scan -- found here by waves 1-3.
 // The shares are NOT equal ("unequal shares"): the CUs of the odd XCDs of an MI355X store this stream ~20 %
-// slower than those of the even ones, so every pair of shares is cut into a LARGE and a SMALL slot (slot_fine_parts) and a
-// workgroup takes the next free large slot if it runs on an even XCD (HW_REG_XCC_ID; blockIdx.x says nothing about the
-// XCD), the next free small one otherwise: two counters (and a third that tells the last workgroup to zero them again),
-// two atomics per workgroup.  Whatever the dispatcher does, gridDim.x workgroups take gridDim.x different slots -- if one
-// kind runs out the other kind is taken.  Equal shares (bias = 0, slot = blockIdx.x) where the launch is not bound by the
-// stores: small stacks, and the host passes bias = 0 for d <= 5.
-// slots: STREAM_SLOT_WORDS zeroed words no other launch in flight uses
-template <class K>
+// slower than those of the even ones, so every pair of shares is cut into a LARGE and a SMALL slot (slot_fine_parts).
+// Workgroups b and b ^ 1 own the two slots of pair b >> 1 and settle between themselves who takes which: the one on an even
+// XCD (HW_REG_XCC_ID; blockIdx.x says nothing about the XCD) prefers the large slot, the first of the two to arrive at the
+// pair's word gets what it prefers, the second takes the other (pair_claim, stream_range.hpp).  One returning atomic per
+// workgroup on a word that only its partner shares: nothing is contended, gridDim.x workgroups take gridDim.x different
+// slots whatever the dispatcher does, and under round-robin dispatch b and b + 1 sit on XCDs of opposite parity, so the even
+// XCD always gets the large slot.  The second arriver stores 0: a launch leaves the words as it found them (graph replay).
+// Equal shares (slot = blockIdx.x, which is the same pair) where the launch is not bound by the stores: small stacks, and
+// the host passes bias = 0 for d <= 5.
+//
+// The start of a launch is a chain of dependent loads on an idle chip, so it is kept to two rounds:
+//   1. with the atomic in flight: offsets[e_begin], offsets[e_end], the table's header and the pair's cut points -- both ends
+//      and the middle for either bias; they serve whichever kind the atomic's answer names.  No table: three find_cut
+//      searches side by side (waves 1-3), which need nothing of the atomic either;
+//   2. offsets[e_lo], offsets[e_hi] -- and, issued right behind them (`prefetch`), the producers' first planes and offsets.
+// slots: one zeroed word per pair, PAIR_WORD_STRIDE dwords apart, that no other launch in flight uses.
+// force_parity (tq_debug_force_xcc_parity): -1 = the XCD's own parity, 0 / 1 = every workgroup claims that one, 2 = inverted
+template <class K, class Prefetch>
 __device__ __forceinline__ bool stream_setup(StreamCtx<typename K::Out>& c, typename K::Lds& S, int64_t capacity,
                                              int64_t e_begin, int64_t e_end, const int32_t* __restrict__ split, int lg, int bias,
-                                             unsigned int* __restrict__ slots, int wave, int lane) {
+                                             unsigned int* __restrict__ slots, int force_parity, int wave, int lane, Prefetch&& prefetch) {
     using L = typename K::L;
+    static_assert(K::NS + K::NPW + K::NP >= 4, "waves 1-3 find the pair's cut points");
     const int RR = (1 << lg) / (int)gridDim.x;
-    // a small stack is not bound by the stores: equal shares, and no counters (their atomic's round trip across the XCDs is
-    // ~3 us at the start of a launch: nothing beside 280 us, a fifth of a 15 us launch)
-    const int64_t p_tab = c.offsets[e_end] - c.offsets[e_begin];   // perspectives of the whole stack
-    if (!slots || bias >= RR || p_tab * (int64_t)(K::NQ * sizeof(typename K::Out)) < (int64_t)(64 << 20)) bias = 0;
-    const bool take = bias > 0;
-    __shared__ int slot_s[2];
-    if (threadIdx.x == 0) {
-        int large = !(blockIdx.x & 1), idx = (int)(blockIdx.x >> 1);
-        if (take) {
-            unsigned xcc;
-            asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-            large = !(xcc & 1u);
-            const unsigned half = gridDim.x >> 1;
-            unsigned t = atomicAdd(&slots[large], 1u);
-            if (t >= half) { large ^= 1; t = atomicAdd(&slots[large], 1u); }
-            idx = t < half ? (int)t : -1;                     // (-1: the counters were not zero when the launch began)
-        }
-        slot_s[0] = large; slot_s[1] = idx;
+    const int pair = (int)(blockIdx.x >> 1);
+    // the claim: the kernel's first memory instruction, before anything is known about the stack.  A small stack ignores the
+    // answer (below), but both arrivals happen, so the word returns to 0 all the same.
+    const bool claim = slots && bias > 0 && !(gridDim.x & 1u);
+    int prefers_large = !(blockIdx.x & 1);
+    unsigned old = 0u;
+    if (threadIdx.x == 0 && claim) {
+        unsigned xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        if (force_parity >= 0) xcc = force_parity < 2 ? (unsigned)force_parity : (xcc ^ 1u);
+        prefers_large = !(xcc & 1u);
+        // (an index the compiler cannot prove uniform: with a uniform address it folds the wave's adds into one and
+        // broadcasts the answer, which waits for the atomic on the spot)
+        unsigned word = (unsigned)(pair * PAIR_WORD_STRIDE);
+        asm volatile("" : "+v"(word));
+        old = atomicAdd(&slots[word], pair_claim(0u, prefers_large).add);
+    }
+    if (!claim || bias >= RR) bias = 0;
+    // round 1, with the atomic in flight: one vector load each, one lane per word (scalar loads would be waited for one by
+    // one) -- the two offsets; the pair's cut points -- [f_lo, f_mid) is its large slot, [f_mid, f_hi) its small one, f_mid
+    // for equal shares and for this bias -- and the table's header.  (Wave 0 has the atomic's answer when it has these:
+    // a wave's loads and returning atomics come back in issue order.  It has nothing else to do until then.)
+    int f_lo, f_eq, f_bias, f_hi;
+    slot_fine_parts(1, pair, RR, 0, f_lo, f_eq);
+    slot_fine_parts(0, pair, RR, bias, f_bias, f_hi);
+    const int64_t ow = c.offsets[lane == 1 ? e_end : e_begin];
+    int32_t tw = 0;
+    if (split) {
+        int fi = cut_header_at(lg) + (lane >= 4 && lane < 4 + CUT_HEADER_WORDS ? lane - 4 : 0);
+        fi = lane == 0 ? f_lo : fi;  fi = lane == 1 ? f_eq : fi;  fi = lane == 2 ? f_bias : fi;  fi = lane == 3 ? f_hi : fi;
+        tw = split[fi];
+    }
+    // A table is followed only if it is the table of THESE offsets over THIS lattice range: its header (cut_points.hpp)
+    // holds the stack's perspective count and the last lattice, and a scan covers [0, N].  The handle matches tables to
+    // offsets POINTERS; a caller who refilled a scanned array hands in a table of another stack -- all zero, say, which
+    // would leave the stack unwritten with nothing latched.  Such a table is not followed: the workgroups find their cut
+    // points themselves.
+    const int64_t off0 = (int64_t)readlane64((uint64_t)ow, 0);
+    int64_t p_all = (int64_t)readlane64((uint64_t)ow, 1) - off0;    // perspectives of the whole stack
+    int64_t cut_lo = __builtin_amdgcn_readlane(tw, 0), cut_eq = __builtin_amdgcn_readlane(tw, 1), cut_bias = __builtin_amdgcn_readlane(tw, 2),
+            cut_hi = __builtin_amdgcn_readlane(tw, 3);
+    const bool by_tab = split && cut_header_words_match(__builtin_amdgcn_readlane(tw, 4), __builtin_amdgcn_readlane(tw, 5),
+                                                        __builtin_amdgcn_readlane(tw, 6), p_all, e_begin, e_end);
+    // a small stack is not bound by the stores: equal shares
+    if (p_all * (int64_t)(K::NQ * sizeof(typename K::Out)) < (int64_t)(64 << 20)) bias = 0;
+    int64_t cut_mid = bias ? cut_bias : cut_eq;
+    __shared__ int64_t cut_s[3];
+    __shared__ int kind_s;
+    if (!by_tab && wave >= 1 && wave <= 3) {                 // (not wave 0: its loads come back behind the atomic)
+        const int64_t e = find_cut(c.offsets, e_begin, e_end, wave == 1 ? f_lo : (wave == 2 ? (bias ? f_bias : f_eq) : f_hi), lg, lane);
+        if (lane == 0) cut_s[wave - 1] = e;
     }
     // (the rings and hand-off words meanwhile: they do not depend on the range)
-    for (uint32_t i = threadIdx.x; i < (K::BMASK + 1u) / 4; i += blockDim.x) reinterpret_cast<uint4*>(S.bits)[i] = make_uint4(0u, 0u, 0u, 0u);
+    constexpr uint32_t THREADS = 64u * (K::NS + K::NPW + K::NP);    // (blockDim.x would be one more load to wait for)
+    for (uint32_t i = threadIdx.x; i < (K::BMASK + 1u) / 4; i += THREADS) reinterpret_cast<uint4*>(S.bits)[i] = make_uint4(0u, 0u, 0u, 0u);
     if (threadIdx.x == 0) S.abort = 0u;
     if (threadIdx.x < K::NP) S.pq[threadIdx.x] = 0u;
     if (threadIdx.x < K::NPW) S.pcons[threadIdx.x] = 0u;
     if (threadIdx.x < K::NS) S.cons[threadIdx.x] = 0u;       // (a lower bound of "the first element storer s has not taken yet")
-    __syncthreads();
-    if (threadIdx.x == 64 * K::NS && take) {                 // (a positions wave: thread 0's wave stores the range's first window)
-        // the last workgroup to have taken its slot leaves the counters zero for the next launch that uses them
-        // (also a replay of this very launch from a captured graph): nobody else touches them any more.  Off the
-        // critical path: only this thread's wave waits for the answer.
-        __threadfence();
-        if (atomicAdd(&slots[2], 1u) == gridDim.x - 1u) { slots[0] = 0u; slots[1] = 0u; __threadfence(); slots[2] = 0u; }
+    if (threadIdx.x == 0) {                                  // the atomic's answer
+        const PairClaim pc = pair_claim(old, prefers_large);
+        if (claim && pc.second) __hip_atomic_store(&slots[pair * PAIR_WORD_STRIDE], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        kind_s = claim ? pc.kind : prefers_large;
     }
-    if (slot_s[1] < 0) {
+    __syncthreads();
+    int kind = kind_s;
+    if (kind < 0) {                                          // the pair's word was not zero when the launch began
         if (threadIdx.x == 0) atomicOr(c.err, ERR_INTERNAL);
         return false;
     }
-    int f_lo, f_hi;
-    slot_fine_parts(slot_s[0], slot_s[1], RR, bias, f_lo, f_hi);
-    // A table is followed only if it is the table of THESE offsets over THIS lattice range: its header (cut_points.hpp) holds
-    // the stack's perspective count and the last lattice, and a scan covers [0, N].  The handle matches tables to offsets
-    // POINTERS; a caller who refilled a scanned array hands in a table of another stack -- all zero, say, which would leave
-    // the stack unwritten with nothing latched.  Such a table is not followed: the workgroups find their cut points themselves.
-    const bool by_tab = split && cut_header_matches(split, lg, p_tab, e_begin, e_end);
-    int64_t e_lo, e_hi;
-    if (by_tab) {
-        e_lo = split[f_lo]; e_hi = split[f_hi];
-    } else {
-        __shared__ int64_t cut[2];
-        if (wave < 2) {
-            const int64_t e = find_cut(c.offsets, e_begin, e_end, wave ? f_hi : f_lo, lg, lane);
-            if (lane == 0) cut[wave] = e;
-        }
-        __syncthreads();
-        e_lo = cut[0]; e_hi = cut[1];
-    }
+    if (!bias) kind = !(blockIdx.x & 1);                     // equal shares: slot = blockIdx.x
+    if (!by_tab) { cut_lo = cut_s[0]; cut_mid = cut_s[1]; cut_hi = cut_s[2]; }
+    int64_t e_lo = kind ? cut_lo : cut_mid, e_hi = kind ? cut_mid : cut_hi;
     e_lo = e_lo < e_begin ? e_begin : (e_lo > e_end ? e_end : e_lo);       // whatever the table holds, stay inside the range
     e_hi = e_hi < e_lo ? e_lo : (e_hi > e_end ? e_end : e_hi);
-    const int64_t off0 = c.offsets[e_begin];
-    int64_t p_all = c.offsets[e_end] - off0;                 // perspectives of the whole stack
     int64_t e_stop = e_end;
     if (p_all > capacity) {                                  // stack does not fit: only the lattices that fit whole are written
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(c.err, ERR_CAPACITY);
@@ -316,7 +341,10 @@ __device__ __forceinline__ bool stream_setup(StreamCtx<typename K::Out>& c, type
         e_lo = e_lo < e_stop ? e_lo : e_stop;
         e_hi = e_hi < e_stop ? e_hi : e_stop;
     }
-    const int64_t Q0 = c.offsets[e_lo] - off0, Q1 = c.offsets[e_hi] - off0;    // perspective range [Q0, Q1)
+    // round 2: one vector load again, and behind it the producers' first planes and offsets
+    const int64_t qw = c.offsets[lane == 1 ? e_hi : e_lo];
+    prefetch(e_lo, e_stop);
+    const int64_t Q0 = (int64_t)readlane64((uint64_t)qw, 0) - off0, Q1 = (int64_t)readlane64((uint64_t)qw, 1) - off0;    // perspective range [Q0, Q1)
     // The offsets come from the caller: whatever they hold, nothing is stored outside [0, p_all) perspectives.  Offsets
     // that are not monotone over this workgroup's cut points are refused here; offsets that do not match the lattices'
     // own hit counts are refused by the producer that meets the first such lattice.
@@ -496,9 +524,33 @@ __device__ __forceinline__ void emit_hit(const ProdTables<K::D>& PT, uint32_t* b
     const auto ov = PS::roll_cols_masked(a, cs, low), op = PS::roll_cols_masked(c, cs, low);
     if (has_stack) emit_at<K::D>(pos, ov, op, [&](uint32_t idx, uint32_t val) { atomicOr(&bits[idx & K::BMASK], val); });
 }
-// Producer p takes the lattices e_lo + p, e_lo + p + NP, ... of the range, one at a time, 64 hits per pass
+// The planes and offsets of a producer wave's next 64 lattices, one lattice per lane (e_lo + Lb + lane * NP + p), in one
+// round of vector loads.  The first round is issued by the set-up, in front of its own last loads: the addresses need the
+// range's first lattice only, the values are used when the range is known.
+template <class K>
+struct ProducerLoads {
+    uint64_t vv[K::L::W], pp[K::L::W];
+    int64_t oo, oo1;                                           // offsets[e], offsets[e + 1]
+    bool in;                                                   // the lane has a lattice in front of e_stop
+    __device__ __forceinline__ void load(const uint64_t* __restrict__ vp, int64_t N, const int64_t* __restrict__ offsets, int64_t e_lo,
+                                         int64_t e_stop, int64_t Lb, int p, int lane) {
+        constexpr int W = K::L::W;
+        const int64_t e_l = e_lo + Lb + (int64_t)lane * K::NP + p;
+        in = e_l < e_stop;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            vv[k] = in ? vp[(int64_t)k * N + e_l] : 0ull;
+            pp[k] = in ? vp[((int64_t)W + k) * N + e_l] : 0ull;
+        }
+        oo = in ? offsets[e_l] : 0;
+        oo1 = in ? offsets[e_l + 1] : 0;
+    }
+};
+// Producer p takes the lattices e_lo + p, e_lo + p + NP, ... of the range, one at a time, 64 hits per pass.  ld: its first
+// 64 lattices, loaded by the set-up
 template <class K, class Stats>
-__device__ __forceinline__ bool producer_wave(const StreamCtx<typename K::Out>& c, typename K::Lds& S, int p, int lane, Stats& st) {
+__device__ __forceinline__ bool producer_wave(const StreamCtx<typename K::Out>& c, typename K::Lds& S, int p, int lane, Stats& st,
+                                              ProducerLoads<K>& ld) {
     using L = typename K::L;  using B = typename L::B;
     constexpr int W = L::W, NP = K::NP, NQ = K::NQ;
     const bool has_stack = c.r.has_stack, has_pos = c.r.has_pos;
@@ -525,17 +577,11 @@ __device__ __forceinline__ bool producer_wave(const StreamCtx<typename K::Out>& 
         });
     };
     for (int64_t Lb = 0;; Lb += 64 * NP) {
-        // the planes and offsets of this wave's next 64 lattices in one round of vector loads
-        const int64_t e_l = c.e_lo + Lb + (int64_t)lane * NP + p;
-        const bool in = e_l < c.e_stop;
-        uint64_t vv[W], pp[W];
-#pragma unroll
-        for (int k = 0; k < W; ++k) {
-            vv[k] = in ? c.vp[(int64_t)k * c.N + e_l] : 0ull;
-            pp[k] = in ? c.vp[((int64_t)W + k) * c.N + e_l] : 0ull;
-        }
-        const int64_t oo = in ? c.offsets[e_l] - c.off0 : (int64_t)0x7fffffffffffffffll;
-        const int64_t oo1 = in ? c.offsets[e_l + 1] - c.off0 : (int64_t)0x7fffffffffffffffll;
+        if (Lb) ld.load(c.vp, c.N, c.offsets, c.e_lo, c.e_stop, Lb, p, lane);
+        const bool in = ld.in;
+        const uint64_t (&vv)[W] = ld.vv, (&pp)[W] = ld.pp;
+        const int64_t oo = in ? ld.oo - c.off0 : (int64_t)0x7fffffffffffffffll;
+        const int64_t oo1 = in ? ld.oo1 - c.off0 : (int64_t)0x7fffffffffffffffll;
         const uint64_t inmask = __ballot(in && oo < c.QT);   // offsets are monotone: a prefix of the lanes
         if (!inmask) break;
         const int cnt = __popcll(inmask);
@@ -581,21 +627,24 @@ __device__ __forceinline__ bool producer_wave(const StreamCtx<typename K::Out>& 
     return true;
 }
 
-// split / lg / bias / slots: see stream_setup.  stats: see StreamStats
+// split / lg / bias / slots / force_parity: see stream_setup.  stats: see StreamStats
 template <int D, typename OutT, int NS, int NP, int CPW, int RB_LOG, int RP_LOG, bool STATS = false, int NPW = 1>
 __global__ __launch_bounds__(64 * (NS + NPW + NP)) void k_persp_stream(
         const uint64_t* __restrict__ vp, int64_t N, const int64_t* __restrict__ offsets, OutT* __restrict__ out, int32_t* __restrict__ pos,
         int64_t capacity, int* __restrict__ err, int64_t e_begin, int64_t e_end, const int32_t* __restrict__ split, int lg, int bias,
-        unsigned int* __restrict__ slots, unsigned long long* __restrict__ stats = nullptr) {
+        unsigned int* __restrict__ slots, int force_parity, unsigned long long* __restrict__ stats = nullptr) {
     using K = StreamShape<D, OutT, NS, NP, CPW, RB_LOG, RP_LOG, NPW>;
     StreamStats<STATS> st;
     __shared__ typename K::Lds S;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
     StreamCtx<OutT> c{vp, N, offsets, out, pos, err};
-    if (!stream_setup<K>(c, S, capacity, e_begin, e_end, split, lg, bias, slots, wave, lane)) return;
+    ProducerLoads<K> ld;
+    if (!stream_setup<K>(c, S, capacity, e_begin, e_end, split, lg, bias, slots, force_parity, wave, lane, [&](int64_t e_lo, int64_t e_stop) {
+            if (wave >= NS + NPW) ld.load(vp, N, offsets, e_lo, e_stop, 0, wave - NS - NPW, lane);
+        })) return;
     // (false: nothing to do for this role, or the workgroup gave up.  The producer stands first: the kernel is at its SGPR limit,
     // and with the storer first the producer's wave-uniform bitset words are parked in vector lanes: +7 % cycles per lattice, d = 19)
-    const bool done = wave >= NS + NPW ? producer_wave<K>(c, S, wave - NS - NPW, lane, st)
+    const bool done = wave >= NS + NPW ? producer_wave<K>(c, S, wave - NS - NPW, lane, st, ld)
                     : wave < NS        ? storer_wave<K>(c, S, wave, lane, st)
                                        : positions_wave<K>(c, S, wave - NS, lane, st);
     if (done && lane == 0) st.out(stats, NS + NPW + NP, wave);

@@ -26,7 +26,8 @@ struct DeviceCtx {
 };
 constexpr int SPLIT_MAX = 256;       // persistent workgroups of the stack write: one per CU of an MI355X
 constexpr int SPLIT_LG = 13;         // the scan's table cuts the stack into 1 << SPLIT_LG fine parts: 32 per workgroup
-constexpr int N_SLOT_SETS = 8;       // sets of slot counters of the stack write, used in turn
+constexpr int N_SLOT_SETS = 8;       // sets of pair words of the stack write (stream_range.hpp: pair_claim), used in turn
+constexpr int SLOT_SET_WORDS = tq::pair_set_words(SPLIT_MAX);
 // Fine parts (of 32) that the workgroup of an odd XCD hands to its even neighbour (stream_write.hpp: the odd XCDs of an
 // MI355X store ~20 % slower; sweep in profiles/r04_xcd_bias_sweep.txt).  tq_set_xcd_bias / TORICENV_XCD_BIAS = 0..16.
 // Used for d >= 7 and 32- / 16-bit stacks: smaller lattices and the u8 stack are bound by the producers, where unequal
@@ -42,6 +43,8 @@ static int xcd_bias() {
     }
     return b;
 }
+// tq_debug_force_xcc_parity: what the stack write's workgroups take for the parity of their XCD (-1 = what the hardware says)
+static std::atomic<int> g_force_xcc_parity{-1};
 DeviceCtx g_ctx[MAX_DEVICES];
 
 int decode_latch(int flag) {
@@ -125,7 +128,8 @@ int launch_persp_write_t(const uint64_t* vp, int64_t n, const int64_t* offsets, 
         return fail(TQ_E_INVALID, "lattice range too large for one stack write (%lld lattices of d=%d)", (long long)count, D);
     return launch_signal(tq::k_persp_stream<D, OutT, C::NS, C::NP, C::CPW, C::RB, C::RP, false, C::NPW>, dim3(SPLIT_MAX),
                          dim3(64 * (C::NS + C::NPW + C::NP)), stream, done, vp, n, offsets, out, pos, capacity, err, first,
-                         first + count, split, SPLIT_LG, (D >= 7 && sizeof(OutT) >= 2) ? bias : 0, slots, nullptr);
+                         first + count, split, SPLIT_LG, (D >= 7 && sizeof(OutT) >= 2) ? bias : 0, slots,
+                         g_force_xcc_parity.load(std::memory_order_relaxed), nullptr);
 }
 
 // split == nullptr: the cut points did not come with the scan of these offsets (a lattice sub-range, or offsets from
@@ -177,8 +181,8 @@ struct tq_env {            // made by `new tq_env()`: what has no initialiser he
     int32_t* split[2];     // cut points of the stack write, written by the scan (tq_persp_count); two tables take turns, so
     const int64_t* split_for[2];   // the scan of the next step does not overwrite what a running write reads; the offsets
     int split_last;        // array each belongs to, and which one was written last
-    unsigned int* slots;   // N_SLOT_SETS sets of STREAM_SLOT_WORDS counters: the workgroups of a stack write take their shares by XCD (stream_write.hpp)
-    unsigned write_seq;    // and leave them zero; write i uses set i % N, so N writes of one handle may be in flight
+    unsigned int* slots;   // N_SLOT_SETS sets of SLOT_SET_WORDS: one word per pair of workgroups of a stack write, which settle their shares
+    unsigned write_seq;    // by XCD over it (stream_write.hpp) and leave it zero; write i uses set i % N, so N writes of one handle may be in flight
     int xcd_bias = -1;     // this handle's share setting (tq_env_set_xcd_bias), or -1: the process-wide one
     int32_t* sel_need;     // [N] scratch of tq_select_plan: rows of the Q-table each lattice's selection reads,
     int64_t* sel_partial;  // and the level-1 sums of their scan
@@ -201,6 +205,11 @@ int tq_env_set_xcd_bias(tq_env* h, int bias) {
     return TQ_OK;
 }
 int tq_env_get_xcd_bias(const tq_env* h) { return !h ? TQ_E_INVALID : (h->xcd_bias >= 0 ? h->xcd_bias : xcd_bias()); }
+int tq_debug_force_xcc_parity(int parity) {
+    if (parity < -1 || parity > 2) return fail(TQ_E_INVALID, "xcc parity %d outside -1..2", parity);
+    g_force_xcc_parity.store(parity, std::memory_order_relaxed);
+    return TQ_OK;
+}
 
 }  // extern "C"
 
@@ -238,7 +247,7 @@ int tq_create(tq_env** out, int n_envs, int d, int device, uint64_t seed, int64_
     m.zeroed(&h->mark, N * 4);
     m.zeroed(&h->tblock, (size_t)tq::block_bytes(h->w, n_envs));
     for (int32_t*& t : h->split) m.zeroed(&t, (size_t)tq::cut_table_words(SPLIT_LG) * sizeof(int32_t));
-    m.zeroed(&h->slots, N_SLOT_SETS * tq::STREAM_SLOT_WORDS * sizeof(unsigned int));
+    m.zeroed(&h->slots, (size_t)N_SLOT_SETS * SLOT_SET_WORDS * sizeof(unsigned int));
     m.zeroed(&h->sel_need, N * 4 + 32);                         // +32: as for counts
     m.zeroed(&h->sel_partial, ((N + tq::PART_BLOCK - 1) / tq::PART_BLOCK) * 8);
     if (const hipError_t e = m.err; e != hipSuccess) { tq_destroy(h); return fail(TQ_E_HIP, "hipMalloc failed: %s", hipGetErrorString(e)); }
@@ -467,11 +476,23 @@ int tq_persp_write_range_signal(tq_env* h, const int64_t* offsets, int first, in
         if (offsets == h->split_for[h->split_last]) split = h->split[h->split_last];
         else if (offsets == h->split_for[h->split_last ^ 1]) split = h->split[h->split_last ^ 1];
     }
-    unsigned int* slots = h->slots + tq::STREAM_SLOT_WORDS * (h->write_seq++ % N_SLOT_SETS);
+    unsigned int* slots = h->slots + (size_t)SLOT_SET_WORDS * (h->write_seq++ % N_SLOT_SETS);
     return by_size(h->d, [&](auto D) {
         return launch_persp_write<D()>(vp, h->n, offsets, out, positions, capacity, dtype, h->err, stream, first, count, split,
                                        slots, h->xcd_bias >= 0 ? h->xcd_bias : xcd_bias(), done ? done->ev : nullptr);
     });
+}
+
+int tq_debug_slot_words_nonzero(tq_env* h) {
+    void* stream_ = nullptr;
+    ENTER(h, "handle");
+    (void)stream;
+    HIPCHECK(hipDeviceSynchronize());
+    std::vector<unsigned int> w((size_t)N_SLOT_SETS * SLOT_SET_WORDS);
+    HIPCHECK(hipMemcpy(w.data(), h->slots, w.size() * sizeof(unsigned int), hipMemcpyDeviceToHost));
+    int n = 0;
+    for (unsigned int x : w) n += x != 0u;
+    return n;
 }
 
 int tq_persp_write_range(tq_env* h, const int64_t* offsets, int first, int count, void* out, int32_t* positions,
