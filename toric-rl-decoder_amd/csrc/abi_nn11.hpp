@@ -89,7 +89,7 @@ int nn11_forward(const NN11Net& net, const void* stack, int dtype, int64_t rows,
                                                           l == 1 ? stack : out[l - 1], l == 1 ? dtype : 0,
                                                           net.wimg + tq::nn11_wimg_offset(l), net.bias + tq::nn11_bias_offset(l),
                                                           out[l], rows, stream)) return rc;
-    return launch(tq::k_nn11_linear, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, out[L], net.limg, net.lbias, q, rows,
+    return launch(tq::k_nn_linear<64>, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, out[L], net.limg, net.lbias, q, rows,
                   tq::nn11_out_pixels(D));
 }
 }  // namespace

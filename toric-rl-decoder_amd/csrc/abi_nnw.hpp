@@ -25,7 +25,7 @@ template <int D>
 int nnw_conv(int mode, int ks, int nt, const void* in, int dtype, const uint16_t* img, const float* bias, uint16_t* out, int64_t rows,
              hipStream_t stream) {
     constexpr int G = tq::NN11Geom<D>::G, THREADS = tq::NN11Geom<D>::THREADS;
-    const dim3 grid((unsigned)((rows + G - 1) / G), (unsigned)((nt + tq::NNW_NTB - 1) / tq::NNW_NTB)), block(THREADS);
+    const dim3 grid((unsigned)((rows + G - 1) / G), (unsigned)((nt + tq::CONV_NTB - 1) / tq::CONV_NTB)), block(THREADS);
 #define NNW_SHAPE(KS, NT, MODE)                          \
     if (ks == KS && nt == NT && mode == tq::MODE)        \
         return launch(tq::k_nnw_conv<D, KS, NT, tq::MODE>, grid, block, stream, in, dtype, img, bias, out, rows)
@@ -45,11 +45,11 @@ int nnw_forward(const tq_nnw* h, const void* stack, int dtype, int64_t rows, flo
     const int s = h->slot, L = tq::nnw_layers(s);
     for (int l = 1; l <= L; ++l) {
         const int cin = tq::nnw_cin(s, l), cout = tq::nnw_cout(s, l);
-        if (int rc = nnw_conv<D>(tq::nnw_mode(s, l), tq::nnw_ksteps(cin), tq::nnw_ntiles(cout), l == 1 ? stack : h->act[(l - 1) & 1],
+        if (int rc = nnw_conv<D>(tq::nnw_mode(s, l), tq::conv_ksteps(cin), tq::conv_ntiles(cout), l == 1 ? stack : h->act[(l - 1) & 1],
                                  l == 1 ? dtype : 0, h->wimg + tq::nnw_wimg_offset(s, l), h->bias + tq::nnw_bias_offset(s, l),
                                  h->act[l & 1], rows, stream)) return rc;
     }
-    return launch(tq::k_nnw_linear, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, h->act[L & 1], h->limg, h->lbias, q, rows,
+    return launch(tq::k_nn_linear<tq::NNW_FEAT_CP>, dim3((unsigned)((rows + 3) / 4)), dim3(256), stream, h->act[L & 1], h->limg, h->lbias, q, rows,
                   tq::nn11_out_pixels(D));
 }
 }  // namespace

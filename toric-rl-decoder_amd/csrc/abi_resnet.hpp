@@ -30,10 +30,10 @@ struct ResConvArgs {
 template <int D>
 int resnet_conv_full(const tq::ResConv& c, const ResConvArgs& a, hipStream_t stream) {
     constexpr int G = tq::NN11Geom<D>::G, THREADS = tq::NN11Geom<D>::THREADS;
-    const int ks = tq::resnet_ksteps(c.cin), nt = tq::resnet_ntiles(c.cout);
-    const dim3 grid((unsigned)((a.rows + G - 1) / G), (unsigned)((nt + tq::RESNET_NTB - 1) / tq::RESNET_NTB)), block(THREADS);
+    const int ks = tq::conv_ksteps(c.cin), nt = tq::conv_ntiles(c.cout);
+    const dim3 grid((unsigned)((a.rows + G - 1) / G), (unsigned)((nt + tq::CONV_NTB - 1) / tq::CONV_NTB)), block(THREADS);
 #define RESNET_SHAPE(KS, NT, TAPS, STRIDE, STACK)                                                                           \
-    if (ks == KS && nt == NT && c.taps == TAPS && c.stride == STRIDE && tq::resnet_reads_stack(c.cin) == STACK)             \
+    if (ks == KS && nt == NT && c.taps == TAPS && c.stride == STRIDE && tq::conv_reads_stack(c.cin) == STACK)               \
         return launch(tq::k_resnet_conv<D, KS, NT, TAPS, STRIDE, STACK>, grid, block, stream, a.in, a.dtype, a.img, a.scale, a.shift, \
                       a.epi, a.res, a.out, a.rows)
     RESNET_SHAPE(2, 2, 9, 1, true);

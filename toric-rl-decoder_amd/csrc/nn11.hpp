@@ -34,15 +34,30 @@ enum { NN11_CIRCULAR = 0, NN11_ZERO = 1, NN11_VALID = 2, NN11_FULL = 3 };   // N
 enum { NN11_EPI_BIAS_RELU = 0, NN11_EPI_MASK = 1 };                       // what k_nn11_conv does with its sums
 
 TQ_HD int nn11_cpad(int c) { return (c + 31) & ~31; }
+
+// ---- one convolution by its channel counts and taps (9, or 1 for a 1x1), for every net of the library.  The one whose
+// input has 2 channels reads the stack: its weight image has one "tap" whose k runs over (input channel, 3x3 tap).
+constexpr int CONV_NTB = 4;                   // n-tiles of one workgroup where a layer is cut across blockIdx.y
+constexpr int CONV_CHUNK_KS = 8;              // k-steps of one staged chunk, at most
+TQ_HD bool conv_reads_stack(int cin) { return cin == 2; }
+TQ_HD int conv_img_taps(int cin, int taps) { return conv_reads_stack(cin) ? 1 : taps; }    // taps of the weight image
+TQ_HD int conv_kdim(int cin) { return conv_reads_stack(cin) ? 18 : cin; }                  // k values per image tap
+TQ_HD int conv_ksteps(int cin) { return conv_reads_stack(cin) ? 2 : nn11_cpad(cin) / 16; }
+TQ_HD int conv_ntiles(int cout) { return nn11_cpad(cout) / 32; }
+TQ_HD constexpr int conv_chunks(int ksteps) { return (ksteps + CONV_CHUNK_KS - 1) / CONV_CHUNK_KS; }    // equal chunks
+TQ_HD int64_t conv_wimg_elems(int cin, int cout, int taps) {
+    return (int64_t)conv_img_taps(cin, taps) * conv_ksteps(cin) * conv_ntiles(cout) * 512;
+}
+
 // layer l = 1..11
 TQ_HD int nn11_cin(int l) { return NN11_CH[l - 1]; }
 TQ_HD int nn11_cout(int l) { return NN11_CH[l]; }
 TQ_HD int nn11_mode(int l) { return l == 1 ? NN11_CIRCULAR : (l == NN11_LAYERS ? NN11_VALID : NN11_ZERO); }
-TQ_HD int nn11_taps(int l) { return l == 1 ? 1 : 9; }                                  // taps of the weight image
-TQ_HD int nn11_kdim(int l) { return l == 1 ? 18 : nn11_cin(l); }                       // k values per image tap
-TQ_HD int nn11_ksteps(int l) { return l == 1 ? 2 : nn11_cpad(nn11_cin(l)) / 16; }
-TQ_HD int nn11_ntiles(int l) { return nn11_cpad(nn11_cout(l)) / 32; }
-TQ_HD int64_t nn11_wimg_elems(int l) { return (int64_t)nn11_taps(l) * nn11_ksteps(l) * nn11_ntiles(l) * 512; }
+TQ_HD int nn11_taps(int l) { return conv_img_taps(nn11_cin(l), 9); }
+TQ_HD int nn11_kdim(int l) { return conv_kdim(nn11_cin(l)); }
+TQ_HD int nn11_ksteps(int l) { return conv_ksteps(nn11_cin(l)); }
+TQ_HD int nn11_ntiles(int l) { return conv_ntiles(nn11_cout(l)); }
+TQ_HD int64_t nn11_wimg_elems(int l) { return conv_wimg_elems(nn11_cin(l), nn11_cout(l), 9); }
 TQ_HD int64_t nn11_wimg_offset(int l) {            // first element of layer l in the handle's one weight image
     int64_t o = 0;
     for (int i = 1; i < l; ++i) o += nn11_wimg_elems(i);
@@ -99,13 +114,16 @@ TQ_HD NN11WCoord nn11_wimg_coord(int64_t idx, int ksteps, int ntiles) {
 }
 // conv1's k: (input channel, 3x3 tap), 18 values
 TQ_HD int nn11_k1(int cin, int tap) { return cin * 9 + tap; }
-// the value (before rounding) of image element idx of layer l from the torch weight [cout][cin][3][3]; 0 in the padding
-TQ_HD float nn11_wimg_value(int l, int64_t idx, const float* w) {
-    const NN11WCoord c = nn11_wimg_coord(idx, nn11_ksteps(l), nn11_ntiles(l));
-    if (c.cout >= nn11_cout(l) || c.k >= nn11_kdim(l)) return 0.f;
-    if (l == 1) return w[(int64_t)c.cout * 18 + c.k];                   // [cout][cin][ky][kx] with k = cin * 9 + tap
-    return w[((int64_t)c.cout * nn11_cin(l) + c.k) * 9 + c.tap];
+// the value (before rounding) of image element idx from the torch weight [cout][cin][3][3] or [cout][cin][1][1]; 0 in
+// the padding
+TQ_HD float conv_wimg_value(int cin, int cout, int taps, int64_t idx, const float* w) {
+    const NN11WCoord c = nn11_wimg_coord(idx, conv_ksteps(cin), conv_ntiles(cout));
+    if (c.cout >= cout || c.k >= conv_kdim(cin)) return 0.f;
+    if (conv_reads_stack(cin)) return w[(int64_t)c.cout * 18 + c.k];    // [cout][cin][ky][kx] with k = nn11_k1(cin, tap)
+    if (taps == 1) return w[(int64_t)c.cout * cin + c.k];
+    return w[((int64_t)c.cout * cin + c.k) * 9 + c.tap];
 }
+TQ_HD float nn11_wimg_value(int l, int64_t idx, const float* w) { return conv_wimg_value(nn11_cin(l), nn11_cout(l), 9, idx, w); }
 
 // ---- dgrad weight image of layer l = 2..11: the image of the convolution that takes G_l (cout(l) channels) to the
 // gradient of layer l - 1's output (cin(l) channels).  Same fragment order with the two channel counts in each other's
@@ -225,178 +243,72 @@ __device__ __forceinline__ uint16_t nn11_stack_bf16(const void* stack, int dtype
     }
 }
 
-// One conv3x3 + bias + ReLU layer.  KS: k-steps of 16 input channels per tap (conv1: 2 steps over its 18 k values),
-// NT: tiles of 32 output channels, MODE: where a tap's source pixel lies.  `in`: the previous layer's activation image
-// (MODE != CIRCULAR) or the perspective stack [P][2][d][d] of element type `dtype`; `out`: this layer's activation image
-// ((d-2)^2 pixels for NN11_VALID).  Grid: ceil(P / G) workgroups of NN11Geom<D>::THREADS threads.
+}  // namespace tq
+#define TQ_NN11_DEVICE_DECLARATIONS                       // NN11Geom, NN11Rows, nn11_stack_bf16, conv_chunks, ... are declared
+#include "conv_tile.hpp"                                  // conv_tiles, the one tile body, over the declarations above
+namespace tq {
+
+// NN_11's and the wide nets' shape policy (conv_tile.hpp): a 3x3 of stride 1 on the d x d grid, MODE as nn11_src_pixel's.
+template <int D, int MODE>
+struct NN11Shape {
+    static constexpr int SIDE = D, OSIDE = MODE == NN11_VALID ? D - 2 : D;
+    static constexpr int NPIX_IN = MODE == NN11_FULL ? (D - 2) * (D - 2) : D * D, NPIX_OUT = OSIDE * OSIDE;
+    static constexpr int TAPS = 9, STACK = MODE == NN11_CIRCULAR ? CONV_STACK_CIRCULAR : CONV_NO_STACK;
+    TQ_HD static int src(int y, int x, int tap) { return nn11_src_pixel(MODE, D, y, x, tap); }
+};
+
+// The forward's epilogue, NN_11's and the wide nets': relu(sum + bias) over the layer's padded f32 bias.
+struct ConvBiasRelu {
+    const float* bias;
+    __device__ __forceinline__ float4 operator()(const float4& a, int c0, int64_t) const {
+        const float4 b = *reinterpret_cast<const float4*>(bias + c0);
+        return make_float4(fmaxf(a.x + b.x, 0.f), fmaxf(a.y + b.y, 0.f), fmaxf(a.z + b.z, 0.f), fmaxf(a.w + b.w, 0.f));
+    }
+};
+// The dgrad's: the sum where the bf16 activation of `out`'s shape is > 0 (sign clear and not a zero), else 0.
+struct NN11DgradMask {
+    const uint16_t* act;
+    __device__ __forceinline__ float4 operator()(const float4& a, int, int64_t at) const {
+        const uint2 m = *reinterpret_cast<const uint2*>(act + at);
+        return make_float4(nn11_mask((uint16_t)m.x) ? a.x : 0.f, nn11_mask((uint16_t)(m.x >> 16)) ? a.y : 0.f,
+                           nn11_mask((uint16_t)m.y) ? a.z : 0.f, nn11_mask((uint16_t)(m.y >> 16)) ? a.w : 0.f);
+    }
+};
+
+// One conv3x3 layer of NN_11, all n-tiles in one workgroup.  KS: k-steps of 16 input channels per tap (conv1: 2 steps
+// over its 18 k values), NT: tiles of 32 output channels, MODE: where a tap's source pixel lies.  `in`: the previous
+// layer's activation image (MODE != CIRCULAR; (d-2)^2 pixels for NN11_FULL) or the perspective stack [P][2][d][d] of
+// element type `dtype`; `out`: this layer's activation image ((d-2)^2 pixels for NN11_VALID).  Grid: ceil(P / G)
+// workgroups of NN11Geom<D>::THREADS threads.
 // EPI says what becomes of the sums.  NN11_EPI_BIAS_RELU (the forward): `aux` is the layer's padded f32 bias;
-// out = bf16(relu(sum + bias)).  NN11_EPI_MASK (the backward's dgrad over a dgrad image; NN11_FULL reads a (d-2)^2
-// image): `aux` is the bf16 activation image of `out`'s shape; out = bf16(sum where the activation is > 0, else 0).
-// GATHER (conv1 only; ROWS is then NN11Rows, one more argument `g`, and empty otherwise, so that the kernels without it
-// keep their argument list): perspective i of the call is row g.rows[i] of the stack `in` -- any list, unsorted, with
-// repeats.  An index outside [0, g.stack_rows) stages zeros, reads nothing and sets NN11_ERR_INDEX in g.latch.
+// out = bf16(relu(sum + bias)).  NN11_EPI_MASK (the backward's dgrad over a dgrad image): `aux` is the bf16 activation
+// image of `out`'s shape; out = bf16(sum where the activation is > 0, else 0).
+// GATHER (conv1 only; ROWS is then NN11Rows, one more argument, and empty otherwise, so that the kernels without it keep
+// their argument list): the row list of conv_tiles.
 template <int D, int KS, int NT, int MODE, int EPI = NN11_EPI_BIAS_RELU, bool GATHER = false, typename... ROWS>
 __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nn11_conv(const void* __restrict__ in, int dtype, const uint16_t* __restrict__ wimg,
                                                    const void* __restrict__ aux, uint16_t* __restrict__ out, int64_t P, ROWS... rows_arg) {
     static_assert(!GATHER || MODE == NN11_CIRCULAR, "only conv1 reads the stack");
     static_assert(sizeof...(ROWS) == (GATHER ? 1 : 0), "a gathering conv takes one NN11Rows, the others nothing");
-    using Ge = NN11Geom<D>;
-    constexpr int PIX = Ge::PIX, G = Ge::G, MW = Ge::MW, NW = Ge::NW, THREADS = Ge::THREADS;
-    constexpr int NPIX_OUT = MODE == NN11_VALID ? Ge::OPIX : PIX;
-    constexpr int OD = MODE == NN11_VALID ? D - 2 : D;                      // side of the output grid
-    constexpr int ROWS_OUT = G * NPIX_OUT;
-    constexpr int NPIX_IN = MODE == NN11_FULL ? Ge::OPIX : PIX;             // pixels of one perspective in `in`
-    constexpr int CINP = KS * 16, COUTP = NT * 32;
-    // LDS: the workgroup's input rows, channels last, 16 bytes of padding per row (consecutive rows start in different
-    // banks: the 16-byte fragment reads of 8 neighbouring pixels are conflict-free); conv1 stages its G x 2 x d^2 stack
-    // elements as bf16 instead.
-    constexpr int PITCH = CINP * 2 + 16;
-    constexpr int LDS_BYTES = MODE == NN11_CIRCULAR ? ((G * 2 * PIX * 2 + 15) & ~15) : Ge::LROWS * PITCH;
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t persp0 = (int64_t)blockIdx.x * G;
-    const int np = (int)(P - persp0 < G ? P - persp0 : G);                  // perspectives of this workgroup
-
-    if constexpr (MODE == NN11_CIRCULAR) {
-        uint16_t* s = reinterpret_cast<uint16_t*>(lds);
-        if constexpr (GATHER) {
-            const NN11Rows& g = nn11_rows_arg(rows_arg...);
-            for (int i = tid; i < G * 2 * PIX; i += THREADS) {
-                uint16_t v = 0;
-                if (i < np * 2 * PIX) {
-                    const int p = i / (2 * PIX), c = i - p * (2 * PIX);
-                    const int64_t row = g.rows[persp0 + p];
-                    if (row >= 0 && row < g.stack_rows) v = nn11_stack_bf16(in, dtype, row * (2 * PIX) + c);
-                    else if (c == 0) atomicOr(g.latch, NN11_ERR_INDEX);
-                }
-                s[i] = v;
-            }
-        } else {
-            for (int i = tid; i < G * 2 * PIX; i += THREADS)
-                s[i] = i < np * 2 * PIX ? nn11_stack_bf16(in, dtype, persp0 * 2 * PIX + i) : (uint16_t)0;
-        }
-    } else {
-        const uint4* src = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(in) + persp0 * NPIX_IN * CINP);
-        constexpr int CH16 = CINP / 8;                                      // 16-byte chunks per row
-        for (int c = tid; c < Ge::LROWS * CH16; c += THREADS) {
-            const int row = c / CH16, cc = c % CH16;
-            const uint4 v = row < np * NPIX_IN ? src[c] : make_uint4(0, 0, 0, 0);
-            *reinterpret_cast<uint4*>(lds + row * PITCH + cc * 16) = v;
-        }
-    }
-    __syncthreads();
-
-    // this lane's output pixel in each of the wave's tiles (tile i of wave w is tile NW i + w)
-    const int r = lane & 31, h = lane >> 5;
-    int py[MW], px[MW], pbase[MW];                                          // pbase < 0: no such row
-#pragma unroll
-    for (int i = 0; i < MW; ++i) {
-        const int row = (NW * i + wave) * 32 + r;
-        const int p = row / NPIX_OUT, q = row % NPIX_OUT;
-        py[i] = q / OD; px[i] = q % OD;
-        pbase[i] = row < ROWS_OUT ? p * NPIX_IN : -1;
-    }
-
-    nn11_f32x16 acc[MW][NT];
-#pragma unroll
-    for (int i = 0; i < MW; ++i)
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][n][e] = 0.f;
-
-    const uint4* wfrag = reinterpret_cast<const uint4*>(wimg) + lane;       // fragment f: wfrag[f * 64]
-
-    if constexpr (MODE == NN11_CIRCULAR) {
-        const uint16_t* s = reinterpret_cast<const uint16_t*>(lds);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            uint4 w[NT];
-#pragma unroll
-            for (int n = 0; n < NT; ++n) w[n] = wfrag[(ks * NT + n) * 64];
-#pragma unroll
-            for (int i = 0; i < MW; ++i) {
-                if ((NW * i + wave) * 32 >= ROWS_OUT) continue;              // wave-uniform
-                union { uint16_t e[8]; uint4 v; } a;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 16 * ks + 8 * h + j;
-                    uint16_t v = 0;
-                    if (k < 18 && pbase[i] >= 0)
-                        v = s[2 * pbase[i] + (k / 9) * PIX + nn11_src_pixel(NN11_CIRCULAR, D, py[i], px[i], k % 9)];
-                    a.e[j] = v;
-                }
-#pragma unroll
-                for (int n = 0; n < NT; ++n)
-                    acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nn11_bf16x8, w[n]),
-                                                                        __builtin_bit_cast(nn11_bf16x8, a.v), acc[i][n], 0, 0, 0);
-            }
-        }
-    } else {
-        for (int tap = 0; tap < 9; ++tap) {
-            int arow[MW];                                                   // LDS byte address of the lane's source row
-#pragma unroll
-            for (int i = 0; i < MW; ++i) {
-                const int sp = pbase[i] >= 0 ? nn11_src_pixel(MODE, D, py[i], px[i], tap) : -1;
-                arow[i] = (sp >= 0 ? pbase[i] + sp : Ge::ZROW) * PITCH + h * 16;
-            }
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                uint4 w[NT];
-#pragma unroll
-                for (int n = 0; n < NT; ++n) w[n] = wfrag[((tap * KS + ks) * NT + n) * 64];
-#pragma unroll
-                for (int i = 0; i < MW; ++i) {
-                    if ((NW * i + wave) * 32 >= ROWS_OUT) continue;          // wave-uniform
-                    const uint4 a = *reinterpret_cast<const uint4*>(lds + arow[i] + ks * 32);
-#pragma unroll
-                    for (int n = 0; n < NT; ++n)
-                        acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nn11_bf16x8, w[n]),
-                                                                            __builtin_bit_cast(nn11_bf16x8, a), acc[i][n], 0, 0, 0);
-                }
-            }
-        }
-    }
-
-    // epilogue: accumulator register 4 g + q of lane (r, h) = output channel 32 n + 8 g + 4 h + q of pixel r
-#pragma unroll
-    for (int i = 0; i < MW; ++i) {
-        const int row = (NW * i + wave) * 32 + r;
-        if (row >= np * NPIX_OUT || pbase[i] < 0) continue;
-        uint16_t* o = out + (persp0 * NPIX_OUT + row) * COUTP;
-#pragma unroll
-        for (int n = 0; n < NT; ++n)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c0 = 32 * n + 8 * g + 4 * h;
-                float v0, v1, v2, v3;
-                if constexpr (EPI == NN11_EPI_BIAS_RELU) {
-                    const float4 b = *reinterpret_cast<const float4*>(static_cast<const float*>(aux) + c0);
-                    v0 = fmaxf(acc[i][n][4 * g + 0] + b.x, 0.f); v1 = fmaxf(acc[i][n][4 * g + 1] + b.y, 0.f);
-                    v2 = fmaxf(acc[i][n][4 * g + 2] + b.z, 0.f); v3 = fmaxf(acc[i][n][4 * g + 3] + b.w, 0.f);
-                } else {                                                    // bf16 > 0: sign clear and not a zero
-                    const uint2 m = *reinterpret_cast<const uint2*>(static_cast<const uint16_t*>(aux) + (persp0 * NPIX_OUT + row) * COUTP + c0);
-                    v0 = nn11_mask((uint16_t)m.x) ? acc[i][n][4 * g + 0] : 0.f; v1 = nn11_mask((uint16_t)(m.x >> 16)) ? acc[i][n][4 * g + 1] : 0.f;
-                    v2 = nn11_mask((uint16_t)m.y) ? acc[i][n][4 * g + 2] : 0.f; v3 = nn11_mask((uint16_t)(m.y >> 16)) ? acc[i][n][4 * g + 3] : 0.f;
-                }
-                uint2 pk;
-                pk.x = (uint32_t)nn11_bf16(v0) | ((uint32_t)nn11_bf16(v1) << 16);
-                pk.y = (uint32_t)nn11_bf16(v2) | ((uint32_t)nn11_bf16(v3) << 16);
-                *reinterpret_cast<uint2*>(o + c0) = pk;
-            }
-    }
+    using Shape = NN11Shape<D, MODE>;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[conv_lds_bytes<Shape, KS>()];
+    if constexpr (EPI == NN11_EPI_BIAS_RELU)
+        conv_tiles<Shape, KS, NT, NT>(lds, 0, in, dtype, wimg, out, P, ConvBiasRelu{static_cast<const float*>(aux)}, rows_arg...);
+    else
+        conv_tiles<Shape, KS, NT, NT>(lds, 0, in, dtype, wimg, out, P, NN11DgradMask{static_cast<const uint16_t*>(aux)}, rows_arg...);
 }
 
-// The linear layer: one wavefront per perspective over conv11's image [P][npix][64]; f32 sums in a fixed order (lane-
-// strided partial sums, then a butterfly over the 64 lanes), + bias, f32 out.
-__global__ __launch_bounds__(256) void k_nn11_linear(const uint16_t* __restrict__ act, const float* __restrict__ limg,
-                                                     const float* __restrict__ lbias, float* __restrict__ q, int64_t P, int npix) {
+// The linear layer of NN_11 (FEAT_CP = 64) and of the wide nets (224): one wavefront per perspective over the last
+// conv's image [P][npix][FEAT_CP] and the linear image f32 [3][npix][FEAT_CP]; f32 sums in a fixed order (lane-strided
+// partial sums over 16-byte chunks of 8 features, then a butterfly over the 64 lanes), + bias, f32 out.
+template <int FEAT_CP>
+__global__ __launch_bounds__(256) void k_nn_linear(const uint16_t* __restrict__ act, const float* __restrict__ limg,
+                                                   const float* __restrict__ lbias, float* __restrict__ q, int64_t P, int npix) {
     const int lane = threadIdx.x & 63;
     const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= P) return;
-    const int chunks = npix * 8;                                            // 16-byte chunks of 8 features
-    const uint4* a = reinterpret_cast<const uint4*>(act + p * npix * 64);
+    const int chunks = npix * (FEAT_CP / 8);
+    const uint4* a = reinterpret_cast<const uint4*>(act + p * npix * FEAT_CP);
     float s[NN11_OUT] = {0.f, 0.f, 0.f};
     for (int c = lane; c < chunks; c += 64) {
         const uint4 v = a[c];
@@ -405,7 +317,7 @@ __global__ __launch_bounds__(256) void k_nn11_linear(const uint16_t* __restrict_
         for (int j = 0; j < 8; ++j) {
             const float x = nn11_f32((uint16_t)(wd[j >> 1] >> (16 * (j & 1))));
 #pragma unroll
-            for (int o = 0; o < NN11_OUT; ++o) s[o] += x * limg[((int64_t)o * npix * 64) + c * 8 + j];
+            for (int o = 0; o < NN11_OUT; ++o) s[o] += x * limg[((int64_t)o * npix * FEAT_CP) + c * 8 + j];
         }
     }
 #pragma unroll

@@ -1,14 +1,14 @@
 // Forward pass of the reference's default Q-network, ResNet18 (src/nn/torch/ResNet.py, BasicBlock nets), and of
 // ResNet34, which has the same layer shapes and other block counts: eval-mode BatchNorm only.  Implicit-GEMM
-// convolutions on v_mfma_f32_32x32x16_bf16 with NN_11's images, fragment order and tile geometry (nn11.hpp), cut like the
-// wide nets' (nnw.hpp): at most RESNET_NTB = 4 n-tiles per workgroup across blockIdx.y, the input channels staged in equal
-// chunks of at most 8 k-steps.  What is new against k_nnw_conv:
-//   - BatchNorm folded at load into two f32 vectors per convolution, scale s = gamma / sqrt(var + eps) and shift
-//     t = beta - mean s; the epilogue is z = acc s + t, [z = z + r,] [ReLU,] one rounding to bf16;
-//   - 1x1 convolutions (the shortcuts), which read the centre pixel, and stride 2 onto the half grid of side
-//     s = (d + 1) / 2: the 3x3 reads (2y + ky - 1, 2x + kx - 1), zero outside, the 1x1 reads (2y, 2x);
-//   - the side of the input grid is the template parameter, even sides included (the half grid of d = 3, 7, 11, ...);
-//   - the stack-reading first layer is zero padded;
+// convolutions on v_mfma_f32_32x32x16_bf16 with NN_11's images, fragment order and tile geometry (nn11.hpp) over the
+// shared tile body (conv_tile.hpp), cut like the wide nets' (nnw.hpp): at most CONV_NTB = 4 n-tiles per workgroup across
+// blockIdx.y.  This family's own:
+//   - the epilogue (ResNetScaleShift): BatchNorm folded at load into two f32 vectors per convolution, scale
+//     s = gamma / sqrt(var + eps) and shift t = beta - mean s; z = acc s + t, [z = z + r,] [ReLU,] one rounding to bf16;
+//   - the shape policy (ResNetShape): 1x1 convolutions (the shortcuts), which read the centre pixel, and stride 2 onto
+//     the half grid of side s = (d + 1) / 2: the 3x3 reads (2y + ky - 1, 2x + kx - 1), zero outside, the 1x1 reads
+//     (2y, 2x); the side of the input grid is the template parameter, even sides included (the half grid of d = 3, 7,
+//     11, ...); the stack-reading first layer is zero padded;
 //   - 512-channel layers: four block rows, four chunks;
 //   - an average-pool head: Q[a] = (sum_c S[c] bf16(W[a][c])) / s^2 + b[a] with S[c] the f32 sum of channel c over the
 //     pixels in pixel order, so the weights do not depend on d.
@@ -34,8 +34,6 @@ constexpr int RESNET_STEM = 64;                       // channels of conv1
 constexpr int RESNET_MAX_CONVS = 36;                  // ResNet34: 1 + 2 x 16 + 3
 constexpr int RESNET_FEAT = 512;                      // channels of the last image: the head's features
 constexpr int RESNET_MAX_CP = 256;                    // an activation image holds max_rows * d^2 * 256 bf16: 512 s^2 <= 256 d^2
-constexpr int RESNET_NTB = 4;                         // n-tiles of one workgroup
-constexpr int RESNET_CHUNK_KS = 8;                    // k-steps of one staged chunk, at most
 
 enum { RESNET_STEM_CONV = 0, RESNET_CONV1 = 1, RESNET_CONV2 = 2, RESNET_SHORTCUT = 3 };       // a convolution's role
 enum { RESNET_EPI_NONE = 0, RESNET_EPI_RELU = 1, RESNET_EPI_ADD_RELU = 2 };                   // what follows z = acc s + t
@@ -72,29 +70,19 @@ TQ_HD ResConv resnet_conv(int s, int i) {
     return ResConv{2, RESNET_STEM, 9, 1, RESNET_STEM_CONV, 0, 0, 0, 0};
 }
 
-// ---- one convolution by its channel counts and taps.  The one whose input has 2 channels reads the stack: its weight
-// image has one "tap" whose k runs over (input channel, 3x3 tap), as NN_11's conv1.
-TQ_HD bool resnet_reads_stack(int cin) { return cin == 2; }
-TQ_HD int resnet_img_taps(int cin, int taps) { return resnet_reads_stack(cin) ? 1 : taps; }
-TQ_HD int resnet_kdim(int cin) { return resnet_reads_stack(cin) ? 18 : cin; }
-TQ_HD int resnet_ksteps(int cin) { return resnet_reads_stack(cin) ? 2 : nn11_cpad(cin) / 16; }
-TQ_HD int resnet_ntiles(int cout) { return nn11_cpad(cout) / 32; }
-TQ_HD int resnet_chunks(int ksteps) { return (ksteps + RESNET_CHUNK_KS - 1) / RESNET_CHUNK_KS; }
-TQ_HD int64_t resnet_wimg_elems(int cin, int cout, int taps) {
-    return (int64_t)resnet_img_taps(cin, taps) * resnet_ksteps(cin) * resnet_ntiles(cout) * 512;
-}
-// the value (before rounding) of image element idx from the torch weight [cout][cin][3][3] or [cout][cin][1][1]
-TQ_HD float resnet_wimg_value(int cin, int cout, int taps, int64_t idx, const float* w) {
-    const NN11WCoord c = nn11_wimg_coord(idx, resnet_ksteps(cin), resnet_ntiles(cout));
-    if (c.cout >= cout || c.k >= resnet_kdim(cin)) return 0.f;
-    if (resnet_reads_stack(cin)) return w[(int64_t)c.cout * 18 + c.k];          // k = nn11_k1(cin, tap)
-    if (taps == 1) return w[(int64_t)c.cout * cin + c.k];
-    return w[((int64_t)c.cout * cin + c.k) * 9 + c.tap];
-}
-// where convolution i lies in the handle's one weight image and in its scale and shift arrays (i = convs: their sizes)
+// ---- one convolution by its channel counts and taps: one-line calls into nn11.hpp's conv_* functions, as NN_11's
+// by-layer functions are.  The names stay because the host shim (tests/host_resnet_shim.cpp) uses them.
+TQ_HD bool resnet_reads_stack(int cin) { return conv_reads_stack(cin); }
+TQ_HD int resnet_img_taps(int cin, int taps) { return conv_img_taps(cin, taps); }
+TQ_HD int resnet_ksteps(int cin) { return conv_ksteps(cin); }
+TQ_HD int resnet_ntiles(int cout) { return conv_ntiles(cout); }
+TQ_HD int resnet_chunks(int ksteps) { return conv_chunks(ksteps); }
+TQ_HD int64_t resnet_wimg_elems(int cin, int cout, int taps) { return conv_wimg_elems(cin, cout, taps); }
+
+// ---- where convolution i lies in the handle's one weight image and in its scale and shift arrays (i = convs: their sizes)
 TQ_HD int64_t resnet_wimg_offset(int s, int i) {
     int64_t o = 0;
-    for (int j = 0; j < i; ++j) { const ResConv c = resnet_conv(s, j); o += resnet_wimg_elems(c.cin, c.cout, c.taps); }
+    for (int j = 0; j < i; ++j) { const ResConv c = resnet_conv(s, j); o += conv_wimg_elems(c.cin, c.cout, c.taps); }
     return o;
 }
 TQ_HD int resnet_st_offset(int s, int i) {
@@ -127,8 +115,8 @@ TQ_HD float resnet_lin_value(int64_t idx, const float* w) { return nn11_f32(nn11
 // ---- host-side pack (what k_resnet_pack does on the device), for the header's unit test
 inline void resnet_pack_conv_host(int cin, int cout, int taps, const float* w, const float* gamma, const float* beta, const float* mean,
                                   const float* var, float eps, uint16_t* wimg, float* scale, float* shift) {
-    const int64_t n = resnet_wimg_elems(cin, cout, taps);
-    for (int64_t i = 0; i < n; ++i) wimg[i] = nn11_bf16(resnet_wimg_value(cin, cout, taps, i, w));
+    const int64_t n = conv_wimg_elems(cin, cout, taps);
+    for (int64_t i = 0; i < n; ++i) wimg[i] = nn11_bf16(conv_wimg_value(cin, cout, taps, i, w));
     const int cp = nn11_cpad(cout);
     for (int c = 0; c < cp; ++c) {
         const ResFold f = c < cout ? resnet_fold(gamma[c], beta[c], mean[c], var[c], eps) : ResFold{0.f, 0.f};
@@ -152,9 +140,9 @@ __global__ __launch_bounds__(256) void k_resnet_pack(ResNetPack p, int s, float 
     const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) {
         const ResConv c = resnet_conv(s, i);
-        const int64_t elems = resnet_wimg_elems(c.cin, c.cout, c.taps);
+        const int64_t elems = conv_wimg_elems(c.cin, c.cout, c.taps);
         uint16_t* img = wimg + resnet_wimg_offset(s, i);
-        for (int64_t e = t; e < elems; e += stride) img[e] = nn11_bf16(resnet_wimg_value(c.cin, c.cout, c.taps, e, p.w[i]));
+        for (int64_t e = t; e < elems; e += stride) img[e] = nn11_bf16(conv_wimg_value(c.cin, c.cout, c.taps, e, p.w[i]));
         if (t < nn11_cpad(c.cout)) {
             const ResFold f = t < c.cout ? resnet_fold(p.bn[i][0][t], p.bn[i][1][t], p.bn[i][2][t], p.bn[i][3][t], eps) : ResFold{0.f, 0.f};
             const int o = resnet_st_offset(s, i) + (int)t;
@@ -166,145 +154,33 @@ __global__ __launch_bounds__(256) void k_resnet_pack(ResNetPack p, int s, float 
     }
 }
 
-// The n-tiles n0 .. n0 + NTB - 1 of one convolution for the workgroup's G perspectives; `lds`: the kernel's tile.  See
-// k_resnet_conv.
-template <int S, int KS, int NT, int TAPS, int STRIDE, bool STACK, int NTB>
-__device__ __forceinline__ void resnet_conv_tiles(unsigned char* lds, int n0, const void* __restrict__ in, int dtype,
-                                                  const uint16_t* __restrict__ wimg, const float* __restrict__ scale,
-                                                  const float* __restrict__ shift, int epi, const uint16_t* __restrict__ res,
-                                                  uint16_t* __restrict__ out, int64_t P) {
-    using Ge = NN11Geom<S>;
-    constexpr int PIX = Ge::PIX, G = Ge::G, MW = Ge::MW, NW = Ge::NW, THREADS = Ge::THREADS;
-    constexpr int OS = STRIDE == 2 ? (S + 1) / 2 : S;                       // side of the output grid
-    constexpr int NPIX_OUT = OS * OS;
-    constexpr int ROWS_OUT = G * NPIX_OUT;                                  // <= Ge::ROWS: tiles beyond are skipped
-    constexpr int CINP = KS * 16, COUTP = NT * 32;
-    constexpr int NCHUNK = (KS + RESNET_CHUNK_KS - 1) / RESNET_CHUNK_KS, CK = KS / NCHUNK;    // k-steps of one chunk
-    static_assert(CK * NCHUNK == KS && CK <= RESNET_CHUNK_KS, "the k-steps of a layer are cut into equal chunks");
-    static_assert(!STACK || (TAPS == 9 && STRIDE == 1 && KS == 2), "the stack layer is a 3x3 of stride 1 over 18 k values");
-    constexpr int PITCH = CK * 32 + 16;                                     // as NN_11's: rows start in different banks
+// The ResNets' shape policy (conv_tile.hpp): TAPS_ taps (9, or 1 for a 1x1) at stride STRIDE on the S x S grid; the
+// stack layer is zero padded.
+template <int S, int TAPS_, int STRIDE, bool STACK_>
+struct ResNetShape {
+    static_assert(!STACK_ || STRIDE == 1, "the stack layer has stride 1");
+    static constexpr int SIDE = S, OSIDE = STRIDE == 2 ? (S + 1) / 2 : S;
+    static constexpr int NPIX_IN = S * S, NPIX_OUT = OSIDE * OSIDE;
+    static constexpr int TAPS = TAPS_, STACK = STACK_ ? CONV_STACK_ZERO : CONV_NO_STACK;
+    TQ_HD static int src(int y, int x, int tap) { return resnet_src_pixel(S, STRIDE, TAPS_, y, x, tap); }
+};
 
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int64_t persp0 = (int64_t)blockIdx.x * G;
-    const int np = (int)(P - persp0 < G ? P - persp0 : G);                  // perspectives of this workgroup
-
-    // this lane's output pixel in each of the wave's tiles (tile i of wave w is tile NW i + w)
-    const int r = lane & 31, h = lane >> 5;
-    int py[MW], px[MW], pbase[MW];                                          // pbase < 0: no such row
-#pragma unroll
-    for (int i = 0; i < MW; ++i) {
-        const int row = (NW * i + wave) * 32 + r;
-        const int p = row / NPIX_OUT, q = row % NPIX_OUT;
-        py[i] = q / OS; px[i] = q % OS;
-        pbase[i] = row < ROWS_OUT ? p * PIX : -1;
-    }
-
-    nn11_f32x16 acc[MW][NTB];
-#pragma unroll
-    for (int i = 0; i < MW; ++i)
-#pragma unroll
-        for (int n = 0; n < NTB; ++n)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) acc[i][n][e] = 0.f;
-
-    const uint4* wfrag = reinterpret_cast<const uint4*>(wimg) + (int64_t)n0 * 64 + lane;    // fragment f, tile n0: wfrag[f * 64]
-
-    if constexpr (STACK) {
-        // the stack as bf16, exactly as k_nn11_conv stages it; a tap in the zero padding contributes 0
-        uint16_t* s = reinterpret_cast<uint16_t*>(lds);
-        for (int i = tid; i < G * 2 * PIX; i += THREADS)
-            s[i] = i < np * 2 * PIX ? nn11_stack_bf16(in, dtype, persp0 * 2 * PIX + i) : (uint16_t)0;
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            uint4 w[NTB];
-#pragma unroll
-            for (int n = 0; n < NTB; ++n) w[n] = wfrag[(ks * NT + n) * 64];
-#pragma unroll
-            for (int i = 0; i < MW; ++i) {
-                if ((NW * i + wave) * 32 >= ROWS_OUT) continue;              // wave-uniform
-                union { uint16_t e[8]; uint4 v; } a;
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int k = 16 * ks + 8 * h + j;
-                    uint16_t v = 0;
-                    if (k < 18 && pbase[i] >= 0) {
-                        const int sp = resnet_src_pixel(S, 1, 9, py[i], px[i], k % 9);
-                        if (sp >= 0) v = s[2 * pbase[i] + (k / 9) * PIX + sp];
-                    }
-                    a.e[j] = v;
-                }
-#pragma unroll
-                for (int n = 0; n < NTB; ++n)
-                    acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nn11_bf16x8, w[n]),
-                                                                        __builtin_bit_cast(nn11_bf16x8, a.v), acc[i][n], 0, 0, 0);
-            }
+// The ResNets' epilogue: z = acc s + t, [z = z + r,] [ReLU]; `epi` is the same for every workgroup of a launch.
+struct ResNetScaleShift {
+    const float* scale; const float* shift; int epi; const uint16_t* res;
+    __device__ __forceinline__ float4 operator()(const float4& a, int c0, int64_t at) const {
+        const float4 sc = *reinterpret_cast<const float4*>(scale + c0);
+        const float4 sh = *reinterpret_cast<const float4*>(shift + c0);
+        float4 v = make_float4(a.x * sc.x + sh.x, a.y * sc.y + sh.y, a.z * sc.z + sh.z, a.w * sc.w + sh.w);
+        if (epi == RESNET_EPI_ADD_RELU) {                                   // uniform over the workgroup
+            const uint2 rr = *reinterpret_cast<const uint2*>(res + at);
+            v.x += nn11_f32((uint16_t)rr.x); v.y += nn11_f32((uint16_t)(rr.x >> 16));
+            v.z += nn11_f32((uint16_t)rr.y); v.w += nn11_f32((uint16_t)(rr.y >> 16));
         }
-    } else {
-        const uint4* src = reinterpret_cast<const uint4*>(static_cast<const uint16_t*>(in) + persp0 * PIX * CINP);
-        constexpr int ROW16 = CINP / 8, CH16 = CK * 2;                      // 16-byte pieces of an image row / of its chunk
-        for (int c = 0; c < NCHUNK; ++c) {
-            __syncthreads();                                                // the previous chunk has been read
-            for (int i = tid; i < Ge::LROWS * CH16; i += THREADS) {
-                const int row = i / CH16, cc = i % CH16;
-                const uint4 v = row < np * PIX ? src[row * ROW16 + c * CH16 + cc] : make_uint4(0, 0, 0, 0);
-                *reinterpret_cast<uint4*>(lds + row * PITCH + cc * 16) = v;
-            }
-            __syncthreads();
-            for (int tap = 0; tap < TAPS; ++tap) {
-                int arow[MW];                                               // LDS byte address of the lane's source row
-#pragma unroll
-                for (int i = 0; i < MW; ++i) {
-                    const int sp = pbase[i] >= 0 ? resnet_src_pixel(S, STRIDE, TAPS, py[i], px[i], tap) : -1;
-                    arow[i] = (sp >= 0 ? pbase[i] + sp : Ge::ZROW) * PITCH + h * 16;
-                }
-#pragma unroll
-                for (int ks = 0; ks < CK; ++ks) {
-                    uint4 w[NTB];
-#pragma unroll
-                    for (int n = 0; n < NTB; ++n) w[n] = wfrag[((tap * KS + c * CK + ks) * NT + n) * 64];
-#pragma unroll
-                    for (int i = 0; i < MW; ++i) {
-                        if ((NW * i + wave) * 32 >= ROWS_OUT) continue;      // wave-uniform
-                        const uint4 a = *reinterpret_cast<const uint4*>(lds + arow[i] + ks * 32);
-#pragma unroll
-                        for (int n = 0; n < NTB; ++n)
-                            acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(nn11_bf16x8, w[n]),
-                                                                                __builtin_bit_cast(nn11_bf16x8, a), acc[i][n], 0, 0, 0);
-                    }
-                }
-            }
-        }
+        if (epi != RESNET_EPI_NONE) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        return v;
     }
-
-    // epilogue: accumulator register 4 g + q of lane (r, h) = output channel 32 (n0 + n) + 8 g + 4 h + q of pixel r
-#pragma unroll
-    for (int i = 0; i < MW; ++i) {
-        const int row = (NW * i + wave) * 32 + r;
-        if (row >= np * NPIX_OUT || pbase[i] < 0) continue;
-        const int64_t o = (persp0 * NPIX_OUT + row) * COUTP;
-#pragma unroll
-        for (int n = 0; n < NTB; ++n)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int c0 = 32 * (n0 + n) + 8 * g + 4 * h;
-                const float4 sc = *reinterpret_cast<const float4*>(scale + c0);
-                const float4 sh = *reinterpret_cast<const float4*>(shift + c0);
-                float v0 = acc[i][n][4 * g + 0] * sc.x + sh.x, v1 = acc[i][n][4 * g + 1] * sc.y + sh.y;
-                float v2 = acc[i][n][4 * g + 2] * sc.z + sh.z, v3 = acc[i][n][4 * g + 3] * sc.w + sh.w;
-                if (epi == RESNET_EPI_ADD_RELU) {                           // uniform over the workgroup
-                    const uint2 rr = *reinterpret_cast<const uint2*>(res + o + c0);
-                    v0 += nn11_f32((uint16_t)rr.x); v1 += nn11_f32((uint16_t)(rr.x >> 16));
-                    v2 += nn11_f32((uint16_t)rr.y); v3 += nn11_f32((uint16_t)(rr.y >> 16));
-                }
-                if (epi != RESNET_EPI_NONE) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-                uint2 pk;
-                pk.x = (uint32_t)nn11_bf16(v0) | ((uint32_t)nn11_bf16(v1) << 16);
-                pk.y = (uint32_t)nn11_bf16(v2) | ((uint32_t)nn11_bf16(v3) << 16);
-                *reinterpret_cast<uint2*>(out + o + c0) = pk;
-            }
-    }
-}
+};
 
 // One convolution with its folded BatchNorm.  S: side of the INPUT grid (odd 3..21, or a half side 2..11); KS: k-steps of
 // 16 input channels per tap (the stack layer: 2 steps over its 18 k values); NT: tiles of 32 output channels; TAPS: 9, or
@@ -314,28 +190,26 @@ __device__ __forceinline__ void resnet_conv_tiles(unsigned char* lds, int n0, co
 // `scale` / `shift`: the convolution's padded f32 vectors.  `epi` (the same for every workgroup of a launch):
 // RESNET_EPI_NONE out = bf16(acc s + t); RESNET_EPI_RELU out = bf16(relu(acc s + t)); RESNET_EPI_ADD_RELU
 // out = bf16(relu((acc s + t) + res)) with `res` a bf16 image of out's shape.  `out`: [P][output pixels][32 NT].
-// Grid: (ceil(P / G), ceil(NT / RESNET_NTB)) workgroups of NN11Geom<S>::THREADS threads.
+// Grid: (ceil(P / G), ceil(NT / CONV_NTB)) workgroups of NN11Geom<S>::THREADS threads.
 template <int S, int KS, int NT, int TAPS, int STRIDE, bool STACK>
 __global__ __launch_bounds__(NN11Geom<S>::THREADS) void k_resnet_conv(const void* __restrict__ in, int dtype, const uint16_t* __restrict__ wimg,
                                                      const float* __restrict__ scale, const float* __restrict__ shift, int epi,
                                                      const uint16_t* __restrict__ res, uint16_t* __restrict__ out, int64_t P) {
-    using Ge = NN11Geom<S>;
-    constexpr int NCHUNK = (KS + RESNET_CHUNK_KS - 1) / RESNET_CHUNK_KS, CK = KS / NCHUNK;
-    constexpr int LDS_BYTES = STACK ? ((Ge::G * 2 * Ge::PIX * 2 + 15) & ~15) : Ge::LROWS * (CK * 32 + 16);
-    static_assert(LDS_BYTES <= 122128, "never above k_nnw_conv's tile");
-    __shared__ __attribute__((aligned(16))) unsigned char lds[LDS_BYTES];
-    constexpr int REM = NT % RESNET_NTB;                                    // n-tiles of the last block row, if fewer
-    const int n0 = (int)blockIdx.y * RESNET_NTB;
-    if constexpr (NT < RESNET_NTB) {                                        // 64 output channels: one block row of two
-        resnet_conv_tiles<S, KS, NT, TAPS, STRIDE, STACK, NT>(lds, n0, in, dtype, wimg, scale, shift, epi, res, out, P);
+    using Shape = ResNetShape<S, TAPS, STRIDE, STACK>;
+    __shared__ __attribute__((aligned(16))) unsigned char lds[conv_lds_bytes<Shape, KS>()];
+    const ResNetScaleShift e = {scale, shift, epi, res};
+    constexpr int REM = NT % CONV_NTB;                                      // n-tiles of the last block row, if fewer
+    const int n0 = (int)blockIdx.y * CONV_NTB;
+    if constexpr (NT < CONV_NTB) {                                          // 64 output channels: one block row of two
+        conv_tiles<Shape, KS, NT, NT>(lds, n0, in, dtype, wimg, out, P, e);
     } else {
         if constexpr (REM != 0) {
-            if (n0 + RESNET_NTB > NT) {                                     // uniform over the workgroup
-                resnet_conv_tiles<S, KS, NT, TAPS, STRIDE, STACK, REM>(lds, n0, in, dtype, wimg, scale, shift, epi, res, out, P);
+            if (n0 + CONV_NTB > NT) {                                       // uniform over the workgroup
+                conv_tiles<Shape, KS, NT, REM>(lds, n0, in, dtype, wimg, out, P, e);
                 return;
             }
         }
-        resnet_conv_tiles<S, KS, NT, TAPS, STRIDE, STACK, RESNET_NTB>(lds, n0, in, dtype, wimg, scale, shift, epi, res, out, P);
+        conv_tiles<Shape, KS, NT, CONV_NTB>(lds, n0, in, dtype, wimg, out, P, e);
     }
 }
 
