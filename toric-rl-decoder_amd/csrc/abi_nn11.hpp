@@ -1,10 +1,8 @@
-// The NN_11 forward's entry points of include/toricenv.h (part of toricenv.hip's translation unit), and what they share
-// with the learner step's (abi_nn11_grad.hpp): the packed network on the device, the one launcher of k_nn11_conv and
-// the forward over it.
+// The NN_11 forward's entry points of include/toricenv.h (part of toricenv.hip's translation unit), over the frame all
+// network handles share (abi_forward.hpp), and what they share with the learner step's (abi_nn11_grad.hpp): the packed
+// network on the device, the one launcher of k_nn11_conv and the forward over it.
 #pragma once
-#include <new>
-
-#include "abi_util.hpp"
+#include "abi_forward.hpp"
 #include "nn11_grad.hpp"
 
 namespace {
@@ -29,12 +27,8 @@ struct NN11Net {
     // torch-layout f32 weights and biases (12 device pointers each) -> the images, on `stream`
     int load(int d, const float* const* weights, const float* const* biases, hipStream_t stream) {
         constexpr int L = tq::NN11_LAYERS;
-        if (!weights || !biases) return fail(TQ_E_INVALID, "weights / biases is NULL");
         tq::NN11Pack p;
-        for (int i = 0; i <= L; ++i) {
-            if (!weights[i] || !biases[i]) return fail(TQ_E_INVALID, "weights[%d] / biases[%d] is NULL", i, i);
-            p.w[i] = weights[i]; p.b[i] = biases[i];
-        }
+        if (int rc = pointer_lists(weights, biases, L + 1, p.w, p.b)) return rc;
         if (int rc = launch(tq::k_nn11_pack, dim3(64, L + 1), dim3(256), stream, p, d, wimg, bias, limg, lbias)) return rc;
         if (dimg)
             if (int rc = launch(tq::k_nn11_pack_dgrad, dim3(64, L - 1), dim3(256), stream, p, dimg)) return rc;
@@ -109,26 +103,14 @@ extern "C" {
 int tq_nn11_destroy(tq_nn11* h) { return destroy_handle(h); }
 
 int tq_nn11_create(tq_nn11** out, int d, int64_t max_rows, int device) {
-    if (!out) return fail(TQ_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!tq::size_ok(d)) return bad_size(d);
-    if (max_rows <= 0 || max_rows > (int64_t(1) << 24)) return fail(TQ_E_INVALID, "max_rows must be in 1..2^24 (got %lld)", (long long)max_rows);
-    if (int rc = valid_device(device)) return rc;
-    DeviceGuard guard;
-    if (int rc = guard.enter_device(device)) return rc;
-    tq_nn11* h = new (std::nothrow) tq_nn11();
-    if (!h) return fail(TQ_E_INVALID, "out of host memory");
-    h->d = d; h->device = device; h->max_rows = max_rows;
-    h->net.alloc(h->mem, d, false);
-    for (int i = 0; i < 2; ++i)
-        h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::NN11_MAX_CP * sizeof(uint16_t));
-    for (int l = 1; l <= tq::NN11_LAYERS; ++l) h->out[l] = h->act[(l + 1) & 1];
-    h->mem.zeroed(&h->latch, 16);
-    hipError_t e = h->mem.err;
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) { tq_nn11_destroy(h); return fail(TQ_E_HIP, "nn11 allocation failed: %s", hipGetErrorString(e)); }
-    *out = h;
-    return TQ_OK;
+    return create_handle(out, "nn11", d, device, no_check, [&] { return max_rows_check(max_rows); }, [&](tq_nn11* h) {
+        h->max_rows = max_rows;
+        h->net.alloc(h->mem, d, false);
+        for (int i = 0; i < 2; ++i)
+            h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::NN11_MAX_CP * sizeof(uint16_t));
+        for (int l = 1; l <= tq::NN11_LAYERS; ++l) h->out[l] = h->act[(l + 1) & 1];
+        h->mem.zeroed(&h->latch, 16);
+    });
 }
 
 int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* biases, void* stream_) {
@@ -136,32 +118,12 @@ int tq_nn11_load(tq_nn11* h, const float* const* weights, const float* const* bi
     return h->net.load(h->d, weights, biases, stream);
 }
 
-// what both forwards refuse before any launch; *done: nothing to do (no rows)
-static int nn11_forward_args(const tq_nn11* h, const void* stack, int dtype, int64_t rows, const float* q, bool* done) {
-    *done = false;
-    if (!h->net.loaded) return fail(TQ_E_INVALID, "nn11 forward before tq_nn11_load");
-    if (dtype < TQ_F32 || dtype > TQ_U8) return fail(TQ_E_INVALID, "bad stack dtype %d", dtype);
-    if (rows < 0) return fail(TQ_E_INVALID, "negative rows");
-    if (rows == 0) { *done = true; return TQ_OK; }
-    if (!stack || !q) return fail(TQ_E_INVALID, "stack / q is NULL");
-    REQUIRE_ALIGNED16(stack, "stack");
-    REQUIRE_ALIGNED16(q, "q");
-    return TQ_OK;
-}
-
 int tq_nn11_forward(tq_nn11* h, const void* stack, int dtype, int64_t rows, float* q, void* stream_) {
     ENTER(h, "nn11 handle");
     bool done;
-    if (int rc = nn11_forward_args(h, stack, dtype, rows, q, &done); rc || done) return rc;
-    const int64_t esize = dtype == TQ_F32 ? 4 : (dtype == TQ_U8 ? 1 : 2);
-    const int64_t row_bytes = 2 * (int64_t)h->d * h->d * esize;
-    return by_size(h->d, [&](auto D) {                     // passes of at most max_rows perspectives
-        for (int64_t first = 0; first < rows; first += h->max_rows) {
-            const int64_t n = rows - first < h->max_rows ? rows - first : h->max_rows;
-            if (int rc = nn11_forward<D()>(h->net, static_cast<const char*>(stack) + first * row_bytes, dtype, n, h->out,
-                                           q + first * tq::NN11_OUT, stream)) return rc;
-        }
-        return (int)TQ_OK;
+    if (int rc = forward_args("nn11", h->net.loaded, stack, dtype, rows, q, &done); rc || done) return rc;
+    return forward_passes(h->d, h->max_rows, stack, dtype, false, rows, q, [&](auto D, const void* s, int64_t, int64_t n, float* qn) {
+        return nn11_forward<D()>(h->net, s, dtype, n, h->out, qn, stream);
     });
 }
 
@@ -169,16 +131,11 @@ int tq_nn11_forward_rows(tq_nn11* h, const void* stack, int dtype, int64_t stack
                          void* stream_) {
     ENTER(h, "nn11 handle");
     bool done;
-    if (int rc = nn11_forward_args(h, stack, dtype, n, q, &done); rc || done) return rc;
+    if (int rc = forward_args("nn11", h->net.loaded, stack, dtype, n, q, &done); rc || done) return rc;
     if (stack_rows < 0) return fail(TQ_E_INVALID, "negative stack_rows");
     if (!rows) return fail(TQ_E_INVALID, "rows is NULL");
-    return by_size(h->d, [&](auto D) {                     // passes of at most max_rows perspectives, all over the one stack
-        for (int64_t first = 0; first < n; first += h->max_rows) {
-            const int64_t m = n - first < h->max_rows ? n - first : h->max_rows;
-            if (int rc = nn11_forward<D()>(h->net, stack, dtype, m, h->out, q + first * tq::NN11_OUT, stream,
-                                           tq::NN11Rows{rows + first, stack_rows, h->latch})) return rc;
-        }
-        return (int)TQ_OK;
+    return forward_passes(h->d, h->max_rows, stack, dtype, true, n, q, [&](auto D, const void* s, int64_t first, int64_t m, float* qm) {
+        return nn11_forward<D()>(h->net, s, dtype, m, h->out, qm, stream, tq::NN11Rows{rows + first, stack_rows, h->latch});
     });
 }
 

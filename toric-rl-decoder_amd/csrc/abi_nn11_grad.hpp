@@ -1,7 +1,5 @@
 // The NN_11 learner step's entry points of include/toricenv.h (part of toricenv.hip's translation unit).
 #pragma once
-#include <new>
-
 #include "abi_nn11.hpp"
 
 struct tq_nn11_grad {                      // made by `new tq_nn11_grad()`: every member starts as zero
@@ -75,35 +73,26 @@ extern "C" {
 int tq_nn11_grad_destroy(tq_nn11_grad* h) { return destroy_handle(h); }
 
 int tq_nn11_grad_create(tq_nn11_grad** out, int d, int max_batch, int device) {
-    if (!out) return fail(TQ_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (!tq::size_ok(d)) return bad_size(d);
-    if (max_batch < 1 || max_batch > 4096) return fail(TQ_E_INVALID, "max_batch must be in 1..4096 (got %d)", max_batch);
-    if (int rc = valid_device(device)) return rc;
-    DeviceGuard guard;
-    if (int rc = guard.enter_device(device)) return rc;
-    tq_nn11_grad* h = new (std::nothrow) tq_nn11_grad();
-    if (!h) return fail(TQ_E_INVALID, "out of host memory");
-    h->d = d; h->device = device; h->max_batch = max_batch;
-    constexpr int L = tq::NN11_LAYERS;
-    const size_t n = (size_t)max_batch;
-    h->net.alloc(h->mem, d, true);
-    for (int l = 1; l <= L; ++l)
-        h->mem.zeroed(&h->act[l], n * tq::nn11_layer_pixels(l, d) * tq::nn11_cpad(tq::nn11_cout(l)) * sizeof(uint16_t));
-    for (int i = 0; i < 2; ++i) h->mem.zeroed(&h->g[i], n * d * d * tq::NN11_MAX_CP * sizeof(uint16_t));
-    h->mem.zeroed(&h->q, n * tq::NN11_OUT * sizeof(float));
-    h->mem.zeroed(&h->dq, n * tq::NN11_OUT * sizeof(float));
-    const size_t chunks = (size_t)tq::nn11_wgrad_chunks(d, max_batch);
-    h->mem.zeroed(&h->wpart, chunks * tq::NN11_WPART_ELEMS * sizeof(float));
-    h->mem.zeroed(&h->bpart, chunks * tq::NN11_MAX_CP * sizeof(float));
-    const size_t slices = (n + tq::NN11_LIN_SLICE - 1) / tq::NN11_LIN_SLICE;
-    h->mem.zeroed(&h->lpart, slices * (size_t)tq::nn11_lin_elems(d) * sizeof(float));
-    h->mem.zeroed(&h->latch, 16);
-    hipError_t e = h->mem.err;
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) { tq_nn11_grad_destroy(h); return fail(TQ_E_HIP, "nn11 grad allocation failed: %s", hipGetErrorString(e)); }
-    *out = h;
-    return TQ_OK;
+    auto batch_check = [&] {
+        return max_batch < 1 || max_batch > 4096 ? fail(TQ_E_INVALID, "max_batch must be in 1..4096 (got %d)", max_batch) : (int)TQ_OK;
+    };
+    return create_handle(out, "nn11 grad", d, device, no_check, batch_check, [&](tq_nn11_grad* h) {
+        h->max_batch = max_batch;
+        constexpr int L = tq::NN11_LAYERS;
+        const size_t n = (size_t)max_batch;
+        h->net.alloc(h->mem, d, true);
+        for (int l = 1; l <= L; ++l)
+            h->mem.zeroed(&h->act[l], n * tq::nn11_layer_pixels(l, d) * tq::nn11_cpad(tq::nn11_cout(l)) * sizeof(uint16_t));
+        for (int i = 0; i < 2; ++i) h->mem.zeroed(&h->g[i], n * d * d * tq::NN11_MAX_CP * sizeof(uint16_t));
+        h->mem.zeroed(&h->q, n * tq::NN11_OUT * sizeof(float));
+        h->mem.zeroed(&h->dq, n * tq::NN11_OUT * sizeof(float));
+        const size_t chunks = (size_t)tq::nn11_wgrad_chunks(d, max_batch);
+        h->mem.zeroed(&h->wpart, chunks * tq::NN11_WPART_ELEMS * sizeof(float));
+        h->mem.zeroed(&h->bpart, chunks * tq::NN11_MAX_CP * sizeof(float));
+        const size_t slices = (n + tq::NN11_LIN_SLICE - 1) / tq::NN11_LIN_SLICE;
+        h->mem.zeroed(&h->lpart, slices * (size_t)tq::nn11_lin_elems(d) * sizeof(float));
+        h->mem.zeroed(&h->latch, 16);
+    });
 }
 
 int tq_nn11_grad_load(tq_nn11_grad* h, const float* const* weights, const float* const* biases, void* stream_) {

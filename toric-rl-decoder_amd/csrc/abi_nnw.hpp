@@ -1,9 +1,7 @@
 // The wide nets' forward (NN_8, NN_17): the tq_nnw_* entry points of include/toricenv.h (part of toricenv.hip's
-// translation unit), after abi_nn11.hpp's conventions.
+// translation unit), over the frame all network handles share (abi_forward.hpp).
 #pragma once
-#include <new>
-
-#include "abi_util.hpp"
+#include "abi_forward.hpp"
 #include "nnw.hpp"
 
 struct tq_nnw {                            // made by `new tq_nnw()`: every member starts as zero
@@ -24,8 +22,7 @@ namespace {
 template <int D>
 int nnw_conv(int mode, int ks, int nt, const void* in, int dtype, const uint16_t* img, const float* bias, uint16_t* out, int64_t rows,
              hipStream_t stream) {
-    constexpr int G = tq::NN11Geom<D>::G, THREADS = tq::NN11Geom<D>::THREADS;
-    const dim3 grid((unsigned)((rows + G - 1) / G), (unsigned)((nt + tq::CONV_NTB - 1) / tq::CONV_NTB)), block(THREADS);
+    const auto [grid, block] = conv_dims<D>(rows, nt);
 #define NNW_SHAPE(KS, NT, MODE)                          \
     if (ks == KS && nt == NT && mode == tq::MODE)        \
         return launch(tq::k_nnw_conv<D, KS, NT, tq::MODE>, grid, block, stream, in, dtype, img, bias, out, rows)
@@ -59,41 +56,25 @@ extern "C" {
 int tq_nnw_destroy(tq_nnw* h) { return destroy_handle(h); }
 
 int tq_nnw_create(tq_nnw** out, int net, int d, int64_t max_rows, int device) {
-    if (!out) return fail(TQ_E_INVALID, "out is NULL");
-    *out = nullptr;
     const int s = tq::nnw_slot(net);
-    if (s < 0) return fail(TQ_E_INVALID, "net must be TQ_NET_NN8 or TQ_NET_NN17 (got %d)", net);
-    if (!tq::size_ok(d)) return bad_size(d);
-    if (max_rows <= 0 || max_rows > (int64_t(1) << 24)) return fail(TQ_E_INVALID, "max_rows must be in 1..2^24 (got %lld)", (long long)max_rows);
-    if (int rc = valid_device(device)) return rc;
-    DeviceGuard guard;
-    if (int rc = guard.enter_device(device)) return rc;
-    tq_nnw* h = new (std::nothrow) tq_nnw();
-    if (!h) return fail(TQ_E_INVALID, "out of host memory");
-    h->slot = s; h->d = d; h->device = device; h->max_rows = max_rows;
-    const int L = tq::nnw_layers(s);
-    h->mem.zeroed(&h->wimg, (size_t)tq::nnw_wimg_offset(s, L + 1) * sizeof(uint16_t));
-    h->mem.zeroed(&h->bias, (size_t)tq::nnw_bias_offset(s, L + 1) * sizeof(float));
-    h->mem.zeroed(&h->limg, (size_t)tq::nnw_lin_elems(d) * sizeof(float));
-    h->mem.zeroed(&h->lbias, 16);
-    for (int i = 0; i < 2; ++i)
-        h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::NNW_MAX_CP * sizeof(uint16_t));
-    hipError_t e = h->mem.err;
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) { tq_nnw_destroy(h); return fail(TQ_E_HIP, "nnw allocation failed: %s", hipGetErrorString(e)); }
-    *out = h;
-    return TQ_OK;
+    auto net_check = [&] { return s < 0 ? fail(TQ_E_INVALID, "net must be TQ_NET_NN8 or TQ_NET_NN17 (got %d)", net) : (int)TQ_OK; };
+    return create_handle(out, "nnw", d, device, net_check, [&] { return max_rows_check(max_rows); }, [&](tq_nnw* h) {
+        h->slot = s; h->max_rows = max_rows;
+        const int L = tq::nnw_layers(s);
+        h->mem.zeroed(&h->wimg, (size_t)tq::nnw_wimg_offset(s, L + 1) * sizeof(uint16_t));
+        h->mem.zeroed(&h->bias, (size_t)tq::nnw_bias_offset(s, L + 1) * sizeof(float));
+        h->mem.zeroed(&h->limg, (size_t)tq::nnw_lin_elems(d) * sizeof(float));
+        h->mem.zeroed(&h->lbias, 16);
+        for (int i = 0; i < 2; ++i)
+            h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::NNW_MAX_CP * sizeof(uint16_t));
+    });
 }
 
 int tq_nnw_load(tq_nnw* h, const float* const* weights, const float* const* biases, void* stream_) {
     ENTER(h, "nnw handle");
     const int L = tq::nnw_layers(h->slot);
-    if (!weights || !biases) return fail(TQ_E_INVALID, "weights / biases is NULL");
     tq::NNWPack p = {};
-    for (int i = 0; i <= L; ++i) {
-        if (!weights[i] || !biases[i]) return fail(TQ_E_INVALID, "weights[%d] / biases[%d] is NULL", i, i);
-        p.w[i] = weights[i]; p.b[i] = biases[i];
-    }
+    if (int rc = pointer_lists(weights, biases, L + 1, p.w, p.b)) return rc;
     if (int rc = launch(tq::k_nnw_pack, dim3(64, L + 1), dim3(256), stream, p, h->slot, h->d, h->wimg, h->bias, h->limg, h->lbias)) return rc;
     h->loaded = 1;
     return TQ_OK;
@@ -101,22 +82,10 @@ int tq_nnw_load(tq_nnw* h, const float* const* weights, const float* const* bias
 
 int tq_nnw_forward(tq_nnw* h, const void* stack, int dtype, int64_t rows, float* q, void* stream_) {
     ENTER(h, "nnw handle");
-    if (!h->loaded) return fail(TQ_E_INVALID, "nnw forward before tq_nnw_load");
-    if (dtype < TQ_F32 || dtype > TQ_U8) return fail(TQ_E_INVALID, "bad stack dtype %d", dtype);
-    if (rows < 0) return fail(TQ_E_INVALID, "negative rows");
-    if (rows == 0) return TQ_OK;
-    if (!stack || !q) return fail(TQ_E_INVALID, "stack / q is NULL");
-    REQUIRE_ALIGNED16(stack, "stack");
-    REQUIRE_ALIGNED16(q, "q");
-    const int64_t esize = dtype == TQ_F32 ? 4 : (dtype == TQ_U8 ? 1 : 2);
-    const int64_t row_bytes = 2 * (int64_t)h->d * h->d * esize;
-    return by_size(h->d, [&](auto D) {                     // passes of at most max_rows perspectives
-        for (int64_t first = 0; first < rows; first += h->max_rows) {
-            const int64_t n = rows - first < h->max_rows ? rows - first : h->max_rows;
-            if (int rc = nnw_forward<D()>(h, static_cast<const char*>(stack) + first * row_bytes, dtype, n,
-                                          q + first * tq::NN11_OUT, stream)) return rc;
-        }
-        return (int)TQ_OK;
+    bool done;
+    if (int rc = forward_args("nnw", h->loaded, stack, dtype, rows, q, &done); rc || done) return rc;
+    return forward_passes(h->d, h->max_rows, stack, dtype, false, rows, q, [&](auto D, const void* s, int64_t, int64_t n, float* qn) {
+        return nnw_forward<D()>(h, s, dtype, n, qn, stream);
     });
 }
 

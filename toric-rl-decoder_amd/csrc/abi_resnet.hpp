@@ -1,9 +1,8 @@
 // The BasicBlock ResNets' forward (ResNet18, ResNet34; eval-mode BatchNorm): the tq_resnet_* entry points of
-// include/toricenv.h (part of toricenv.hip's translation unit), after abi_nnw.hpp's conventions.
+// include/toricenv.h (part of toricenv.hip's translation unit), over the frame all network handles share
+// (abi_forward.hpp).
 #pragma once
-#include <new>
-
-#include "abi_util.hpp"
+#include "abi_forward.hpp"
 #include "resnet.hpp"
 
 struct tq_resnet {                         // made by `new tq_resnet()`: every member starts as zero
@@ -29,9 +28,8 @@ struct ResConvArgs {
 // (k-steps, n-tiles, taps, stride): the ten shapes the two nets need at the full grid.
 template <int D>
 int resnet_conv_full(const tq::ResConv& c, const ResConvArgs& a, hipStream_t stream) {
-    constexpr int G = tq::NN11Geom<D>::G, THREADS = tq::NN11Geom<D>::THREADS;
     const int ks = tq::conv_ksteps(c.cin), nt = tq::conv_ntiles(c.cout);
-    const dim3 grid((unsigned)((a.rows + G - 1) / G), (unsigned)((nt + tq::CONV_NTB - 1) / tq::CONV_NTB)), block(THREADS);
+    const auto [grid, block] = conv_dims<D>(a.rows, nt);
 #define RESNET_SHAPE(KS, NT, TAPS, STRIDE, STACK)                                                                           \
     if (ks == KS && nt == NT && c.taps == TAPS && c.stride == STRIDE && tq::conv_reads_stack(c.cin) == STACK)               \
         return launch(tq::k_resnet_conv<D, KS, NT, TAPS, STRIDE, STACK>, grid, block, stream, a.in, a.dtype, a.img, a.scale, a.shift, \
@@ -53,10 +51,9 @@ int resnet_conv_full(const tq::ResConv& c, const ResConvArgs& a, hipStream_t str
 // One convolution over the half grid of side HS: 512 -> 512 is the only shape there.
 template <int HS>
 int resnet_conv_half(const tq::ResConv& c, const ResConvArgs& a, hipStream_t stream) {
-    constexpr int G = tq::NN11Geom<HS>::G, THREADS = tq::NN11Geom<HS>::THREADS;
     if (c.cin != 512 || c.cout != 512 || c.taps != 9 || c.stride != 1)
         return fail(TQ_E_INVALID, "resnet: no half-grid kernel for %d -> %d, %d taps, stride %d", c.cin, c.cout, c.taps, c.stride);
-    const dim3 grid((unsigned)((a.rows + G - 1) / G), 4), block(THREADS);
+    const auto [grid, block] = conv_dims<HS>(a.rows, 16);
     return launch(tq::k_resnet_conv<HS, 32, 16, 9, 1, false>, grid, block, stream, a.in, a.dtype, a.img, a.scale, a.shift, a.epi, a.res,
                   a.out, a.rows);
 }
@@ -95,31 +92,19 @@ extern "C" {
 int tq_resnet_destroy(tq_resnet* h) { return destroy_handle(h); }
 
 int tq_resnet_create(tq_resnet** out, int net, int d, int64_t max_rows, int device) {
-    if (!out) return fail(TQ_E_INVALID, "out is NULL");
-    *out = nullptr;
     const int s = tq::resnet_slot(net);
-    if (s < 0) return fail(TQ_E_INVALID, "net must be TQ_NET_RESNET18 or TQ_NET_RESNET34 (got %d)", net);
-    if (!tq::size_ok(d)) return bad_size(d);
-    if (max_rows <= 0 || max_rows > (int64_t(1) << 24)) return fail(TQ_E_INVALID, "max_rows must be in 1..2^24 (got %lld)", (long long)max_rows);
-    if (int rc = valid_device(device)) return rc;
-    DeviceGuard guard;
-    if (int rc = guard.enter_device(device)) return rc;
-    tq_resnet* h = new (std::nothrow) tq_resnet();
-    if (!h) return fail(TQ_E_INVALID, "out of host memory");
-    h->slot = s; h->d = d; h->device = device; h->max_rows = max_rows;
-    const int n = tq::resnet_convs(s);
-    h->mem.zeroed(&h->wimg, (size_t)tq::resnet_wimg_offset(s, n) * sizeof(uint16_t));
-    h->mem.zeroed(&h->scale, (size_t)tq::resnet_st_offset(s, n) * sizeof(float));
-    h->mem.zeroed(&h->shift, (size_t)tq::resnet_st_offset(s, n) * sizeof(float));
-    h->mem.zeroed(&h->limg, (size_t)tq::resnet_lin_elems() * sizeof(float));
-    h->mem.zeroed(&h->lbias, 16);
-    for (int i = 0; i < 4; ++i)
-        h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::RESNET_MAX_CP * sizeof(uint16_t));
-    hipError_t e = h->mem.err;
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    if (e != hipSuccess) { tq_resnet_destroy(h); return fail(TQ_E_HIP, "resnet allocation failed: %s", hipGetErrorString(e)); }
-    *out = h;
-    return TQ_OK;
+    auto net_check = [&] { return s < 0 ? fail(TQ_E_INVALID, "net must be TQ_NET_RESNET18 or TQ_NET_RESNET34 (got %d)", net) : (int)TQ_OK; };
+    return create_handle(out, "resnet", d, device, net_check, [&] { return max_rows_check(max_rows); }, [&](tq_resnet* h) {
+        h->slot = s; h->max_rows = max_rows;
+        const int n = tq::resnet_convs(s);
+        h->mem.zeroed(&h->wimg, (size_t)tq::resnet_wimg_offset(s, n) * sizeof(uint16_t));
+        h->mem.zeroed(&h->scale, (size_t)tq::resnet_st_offset(s, n) * sizeof(float));
+        h->mem.zeroed(&h->shift, (size_t)tq::resnet_st_offset(s, n) * sizeof(float));
+        h->mem.zeroed(&h->limg, (size_t)tq::resnet_lin_elems() * sizeof(float));
+        h->mem.zeroed(&h->lbias, 16);
+        for (int i = 0; i < 4; ++i)
+            h->mem.zeroed(&h->act[i], (size_t)max_rows * d * d * tq::RESNET_MAX_CP * sizeof(uint16_t));
+    });
 }
 
 int tq_resnet_load(tq_resnet* h, const float* const* conv_weights, const float* const* bn_params, const float* lin_w, const float* lin_b,
@@ -146,22 +131,10 @@ int tq_resnet_load(tq_resnet* h, const float* const* conv_weights, const float* 
 
 int tq_resnet_forward(tq_resnet* h, const void* stack, int dtype, int64_t rows, float* q, void* stream_) {
     ENTER(h, "resnet handle");
-    if (!h->loaded) return fail(TQ_E_INVALID, "resnet forward before tq_resnet_load");
-    if (dtype < TQ_F32 || dtype > TQ_U8) return fail(TQ_E_INVALID, "bad stack dtype %d", dtype);
-    if (rows < 0) return fail(TQ_E_INVALID, "negative rows");
-    if (rows == 0) return TQ_OK;
-    if (!stack || !q) return fail(TQ_E_INVALID, "stack / q is NULL");
-    REQUIRE_ALIGNED16(stack, "stack");
-    REQUIRE_ALIGNED16(q, "q");
-    const int64_t esize = dtype == TQ_F32 ? 4 : (dtype == TQ_U8 ? 1 : 2);
-    const int64_t row_bytes = 2 * (int64_t)h->d * h->d * esize;
-    return by_size(h->d, [&](auto D) {                     // passes of at most max_rows perspectives
-        for (int64_t first = 0; first < rows; first += h->max_rows) {
-            const int64_t n = rows - first < h->max_rows ? rows - first : h->max_rows;
-            if (int rc = resnet_forward<D()>(h, static_cast<const char*>(stack) + first * row_bytes, dtype, n,
-                                             q + first * tq::NN11_OUT, stream)) return rc;
-        }
-        return (int)TQ_OK;
+    bool done;
+    if (int rc = forward_args("resnet", h->loaded, stack, dtype, rows, q, &done); rc || done) return rc;
+    return forward_passes(h->d, h->max_rows, stack, dtype, false, rows, q, [&](auto D, const void* s, int64_t, int64_t n, float* qn) {
+        return resnet_forward<D()>(h, s, dtype, n, qn, stream);
     });
 }
 

@@ -12,15 +12,13 @@ include/toricenv.h).  policy.py re-exports the four classes.
 import ctypes as C
 
 import torch
-import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _lib
+from ._forward import ForwardHandle, PlainConvNet, _check_stack, _pointers
 from ._lib import Handle, _ptr, check, require_gpu, to_device
 
 CHANNELS = (2, 128, 128, 120, 111, 104, 103, 90, 80, 73, 71, 64)
 NAMES = [f"conv{i + 1}" for i in range(11)] + ["linear1"]       # the layers, in the order of every list of 12 below
-_STACK_DTYPES = {torch.float32: _lib.TQ_F32, torch.float16: _lib.TQ_F16, torch.bfloat16: _lib.TQ_BF16, torch.uint8: _lib.TQ_U8}
 
 
 def shapes(d):
@@ -37,43 +35,14 @@ def _check_params(pairs, d, device):
                 raise ValueError(f"{n}: expected contiguous float32 {want} on {device}, got {p.dtype} {tuple(p.shape)} on {p.device}")
 
 
-def _check_stack(x, d, device, what):
-    """A (n, 2, d, d) perspective stack of a dtype the kernels read, on ``device`` -> (contiguous stack, its TQ_* dtype)"""
-    if x.dtype not in _STACK_DTYPES:
-        raise ValueError(f"{what} dtype {x.dtype} not one of float32 / float16 / bfloat16 / uint8")
-    if x.dim() != 4 or tuple(x.shape[1:]) != (2, d, d) or x.device != device:
-        raise ValueError(f"expected a (rows, 2, {d}, {d}) {what} on {device}, got {tuple(x.shape)} on {x.device}")
-    return x.contiguous(), _STACK_DTYPES[x.dtype]
-
-
-def _pointers(tensors):
-    """12 tensors (or None) -> the C array of their device pointers (or None)"""
-    return None if tensors is None else (C.c_void_p * 12)(*[t.data_ptr() for t in tensors])
-
-
-class NN_11(nn.Module):
+class NN_11(PlainConvNet):
     """11 conv3x3 + ReLU then one linear layer (src/nn/torch/NN.py:10-45); the first and the last
     convolution are unpadded after a circular pad of 1 (src/nn/torch/util.py:21-26)."""
 
     CHANNELS = CHANNELS
 
-    def __init__(self, system_size, number_of_actions=3, device=None):
-        super().__init__()
-        ch = self.CHANNELS
-        for i in range(11):
-            pad = 0 if i in (0, 10) else 1
-            setattr(self, f"conv{i + 1}", nn.Conv2d(ch[i], ch[i + 1], kernel_size=3, stride=1, padding=pad))
-        self.linear1 = nn.Linear(64 * (system_size - 2) ** 2, number_of_actions)
-        self.device = device
 
-    def forward(self, x):
-        x = F.pad(x, (1, 1, 1, 1), mode="circular")
-        for i in range(11):
-            x = F.relu(getattr(self, f"conv{i + 1}")(x))
-        return self.linear1(x.flatten(1))
-
-
-class NN11Forward(Handle):
+class NN11Forward(ForwardHandle):
     """NN_11's forward pass as HIP kernels (tq_nn11_*; numerics contract in include/toricenv.h): bf16 weights and
     activations, f32 accumulation, f32 Q-values.  Callable like the model it was made from -- ``f(persp) -> (rows, 3)``
     float32 tensor on the device, for a perspective stack (rows, 2, d, d) of float32, float16, bfloat16 or uint8 -- so
@@ -82,19 +51,14 @@ class NN11Forward(Handle):
     device, no allocation).  Any row count costs the same per row (``any_rows``): _forward_chunked does not pad for it.
     One handle, one stream: calls share the handle's activation scratch, sized for ``max_rows`` rows per pass."""
 
-    any_rows = True
-    _destroy = "tq_nn11_destroy"
+    _create, _forward, _destroy = "tq_nn11_create", "tq_nn11_forward", "tq_nn11_destroy"
+    gathers = True                  # f(persp, rows) reads the listed rows itself: _forward_chunked makes no copy of them
 
     def __init__(self, model_or_state_dict, system_size, device, max_rows=1 << 16):
-        self.device = require_gpu(device)
-        self.system_size = int(system_size)
-        self._L = _lib.load()
-        self._h = C.c_void_p(None)
-        check(self._L.tq_nn11_create(C.byref(self._h), self.system_size, int(max_rows), self.device.index))
-        self.load(model_or_state_dict)
+        super().__init__(model_or_state_dict, system_size, device, max_rows)
 
     def load(self, model_or_state_dict):
-        sd = model_or_state_dict.state_dict() if hasattr(model_or_state_dict, "state_dict") else model_or_state_dict
+        sd = self._state_dict(model_or_state_dict)
         want = {f"{n}.{k}" for n in NAMES for k in ("weight", "bias")}
         if set(sd.keys()) != want:
             raise ValueError(f"state_dict must have exactly NN_11's parameters; differs in {sorted(set(sd.keys()) ^ want)}")
@@ -104,17 +68,13 @@ class NN11Forward(Handle):
         self._call(self._L.tq_nn11_load, _pointers(w), _pointers(b))   # the pack kernel reads w / b on the current stream,
         return self                                                    # where any copies made above are freed in stream order
 
-    gathers = True                  # f(persp, rows) reads the listed rows itself: _forward_chunked makes no copy of them
-
     def __call__(self, persp, rows=None):
         """``rows`` (int32 tensor on the device, any order, repeats allowed): the Q-values of ``persp[rows]`` -- the same
         bits as ``f(persp)[rows]`` -- read from the stack in place (tq_nn11_forward_rows).  An index outside the stack
         gives a Q-row of a zero perspective and makes check() raise."""
-        persp, dtype = _check_stack(persp, self.system_size, self.device, "stack")
         if rows is None:
-            q = torch.empty((persp.shape[0], 3), dtype=torch.float32, device=self.device)
-            self._call(self._L.tq_nn11_forward, _ptr(persp), dtype, persp.shape[0], _ptr(q))
-            return q
+            return super().__call__(persp)
+        persp, dtype = _check_stack(persp, self.system_size, self.device, "stack")
         if rows.dtype != torch.int32 or rows.dim() != 1 or rows.device != self.device:
             raise ValueError(f"rows must be a 1-d int32 tensor on {self.device}, got {rows.dtype} {tuple(rows.shape)} on {rows.device}")
         rows = rows.contiguous()
@@ -127,15 +87,6 @@ class NN11Forward(Handle):
     def check(self):
         """Reads and clears the device error latch (synchronises): ValueError for a row index outside the stack."""
         self._call(self._L.tq_nn11_check)
-
-    def eval(self):
-        return self
-
-    def train(self, mode=True):
-        return self
-
-    def to(self, *args, **kwargs):                         # evaluate() moves its model to the device: it is there already
-        return self
 
 
 class NN11Grad(Handle):

@@ -9,15 +9,11 @@ step and the optimizer of these nets stay with torch on the f32 parameters.  pol
   NN_17          src/nn/torch/NN.py:80-133  20 conv layers despite its name, at most 256 channels
   NNWideForward  either one's forward as bf16 MFMA kernels
 """
-import ctypes as C
-
 import torch
-import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _lib
-from ._lib import Handle, _ptr, check, require_gpu, to_device
-from .nn11 import _check_stack
+from ._forward import ForwardHandle, PlainConvNet, _pointers, match_net
+from ._lib import to_device
 
 CHANNELS = {
     _lib.TQ_NET_NN8: (2, 256, 256, 240, 224, 220, 215, 205, 200),
@@ -38,53 +34,23 @@ def shapes(net, d):
 
 def which_net(sd, d):
     """The net whose parameter names and shapes at size ``d`` the state_dict has exactly; ValueError if neither."""
-    why = []
-    for net, label in ((_lib.TQ_NET_NN8, "NN_8"), (_lib.TQ_NET_NN17, "NN_17")):
-        want = {f"{n}.{k}": s for n, shape in zip(names(net), shapes(net, d)) for k, s in (("weight", shape), ("bias", shape[:1]))}
-        if set(sd.keys()) != set(want):
-            why.append(f"{label}: parameter names differ in {sorted(set(sd.keys()) ^ set(want))[:6]}")
-            continue
-        bad = [k for k, s in want.items() if tuple(sd[k].shape) != s]
-        if not bad:
-            return net
-        why.append(f"{label} at d={d}: {bad[0]} has shape {tuple(sd[bad[0]].shape)}, expected {want[bad[0]]}")
-    raise ValueError("state_dict is neither NN_8's nor NN_17's: " + "; ".join(why))
+    def want(net):
+        return {f"{n}.{k}": s for n, shape in zip(names(net), shapes(net, d)) for k, s in (("weight", shape), ("bias", shape[:1]))}
+    return match_net(sd, [(net, label, want(net)) for net, label in ((_lib.TQ_NET_NN8, "NN_8"), (_lib.TQ_NET_NN17, "NN_17"))],
+                     names="parameter names", at=f" at d={d}")
 
 
-class _WideNet(nn.Module):
-    """conv3x3 + ReLU layers then one linear layer; the first and the last convolution are unpadded after a circular
-    pad of 1 (src/nn/torch/util.py:21-26)."""
-
-    CHANNELS = ()
-
-    def __init__(self, system_size, number_of_actions=3, device=None):
-        super().__init__()
-        ch = self.CHANNELS
-        self.layers = len(ch) - 1
-        for i in range(self.layers):
-            pad = 0 if i in (0, self.layers - 1) else 1
-            setattr(self, f"conv{i + 1}", nn.Conv2d(ch[i], ch[i + 1], kernel_size=3, stride=1, padding=pad))
-        self.linear1 = nn.Linear(ch[-1] * (system_size - 2) ** 2, number_of_actions)
-        self.device = device
-
-    def forward(self, x):
-        x = F.pad(x, (1, 1, 1, 1), mode="circular")
-        for i in range(self.layers):
-            x = F.relu(getattr(self, f"conv{i + 1}")(x))
-        return self.linear1(x.flatten(1))
-
-
-class NN_8(_WideNet):
+class NN_8(PlainConvNet):
     """src/nn/torch/NN.py:47-76."""
     CHANNELS = CHANNELS[_lib.TQ_NET_NN8]
 
 
-class NN_17(_WideNet):
+class NN_17(PlainConvNet):
     """src/nn/torch/NN.py:80-133: twenty conv layers."""
     CHANNELS = CHANNELS[_lib.TQ_NET_NN17]
 
 
-class NNWideForward(Handle):
+class NNWideForward(ForwardHandle):
     """NN_8's or NN_17's forward pass as HIP kernels (tq_nnw_*; numerics contract in include/toricenv.h): bf16 weights
     and activations, f32 accumulation, f32 Q-values.  Callable like the model it was made from -- ``f(persp) -> (rows, 3)``
     float32 tensor on the device, for a perspective stack (rows, 2, d, d) of float32, float16, bfloat16 or uint8 -- so
@@ -95,23 +61,12 @@ class NNWideForward(Handle):
     One handle, one stream: calls share the handle's activation scratch, 2 x max_rows x d^2 x 512 bytes (3.7 GB at
     d = 21 with the default; a larger call is walked in passes of ``max_rows``)."""
 
-    any_rows = True
-    gathers = False
-    _destroy = "tq_nnw_destroy"
+    _create, _forward, _destroy = "tq_nnw_create", "tq_nnw_forward", "tq_nnw_destroy"
 
     def __init__(self, model_or_state_dict, system_size, device, max_rows=1 << 13):
-        self.system_size = int(system_size)
         sd = self._state_dict(model_or_state_dict)
-        self.net = which_net(sd, self.system_size)
-        self.device = require_gpu(device)
-        self._L = _lib.load()
-        self._h = C.c_void_p(None)
-        check(self._L.tq_nnw_create(C.byref(self._h), self.net, self.system_size, int(max_rows), self.device.index))
-        self.load(sd)
-
-    @staticmethod
-    def _state_dict(model_or_state_dict):
-        return model_or_state_dict.state_dict() if hasattr(model_or_state_dict, "state_dict") else model_or_state_dict
+        self.net = which_net(sd, int(system_size))              # a wrong net is refused before the device is asked for
+        super().__init__(sd, system_size, device, max_rows, self.net)
 
     def load(self, model_or_state_dict):
         sd = self._state_dict(model_or_state_dict)
@@ -121,23 +76,5 @@ class NNWideForward(Handle):
         layers = names(net)
         w = [to_device(sd[n + ".weight"].detach(), torch.float32, self.device) for n in layers]
         b = [to_device(sd[n + ".bias"].detach(), torch.float32, self.device) for n in layers]
-        ptrs = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        self._call(self._L.tq_nnw_load, ptrs(w), ptrs(b))           # the pack kernel reads w / b on the current stream,
-        return self                                                 # where any copies made above are freed in stream order
-
-    def __call__(self, persp):
-        persp, dtype = _check_stack(persp, self.system_size, self.device, "stack")
-        q = torch.empty((persp.shape[0], 3), dtype=torch.float32, device=self.device)
-        self._call(self._L.tq_nnw_forward, _ptr(persp), dtype, persp.shape[0], _ptr(q))
-        return q
-
-    forward = __call__
-
-    def eval(self):
-        return self
-
-    def train(self, mode=True):
-        return self
-
-    def to(self, *args, **kwargs):                         # evaluate() moves its model to the device: it is there already
-        return self
+        self._call(self._L.tq_nnw_load, _pointers(w), _pointers(b))  # the pack kernel reads w / b on the current stream,
+        return self                                                  # where any copies made above are freed in stream order

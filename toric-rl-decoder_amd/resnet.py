@@ -10,15 +10,13 @@ backward pass and the optimizer stay with torch on the f32 parameters.  policy.p
   ResNet34       src/nn/torch/ResNet.py  ResNet(BasicBlock, [3, 4, 6, 3]), 36 convolutions
   ResNetForward  either one's eval-mode forward as bf16 MFMA kernels
 """
-import ctypes as C
-
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
-from ._lib import Handle, _ptr, check, require_gpu, to_device
-from .nn11 import _check_stack
+from ._forward import ForwardHandle, _pointers, match_net
+from ._lib import _ptr, to_device
 
 BLOCKS = {_lib.TQ_NET_RESNET18: (2, 2, 2, 2), _lib.TQ_NET_RESNET34: (3, 4, 6, 3)}
 PLANES = (64, 128, 256, 512)
@@ -57,18 +55,8 @@ def shapes(net):
 def which_net(sd):
     """The net whose parameter and buffer names and shapes the state_dict has exactly (``num_batches_tracked`` entries
     are ignored); ValueError if neither."""
-    keys = {k for k in sd.keys() if not k.endswith("num_batches_tracked")}
-    why = []
-    for net, label in ((_lib.TQ_NET_RESNET18, "ResNet18"), (_lib.TQ_NET_RESNET34, "ResNet34")):
-        want = shapes(net)
-        if keys != set(want):
-            why.append(f"{label}: names differ in {sorted(keys ^ set(want))[:6]}")
-            continue
-        bad = [k for k, s in want.items() if tuple(sd[k].shape) != s]
-        if not bad:
-            return net
-        why.append(f"{label}: {bad[0]} has shape {tuple(sd[bad[0]].shape)}, expected {want[bad[0]]}")
-    raise ValueError("state_dict is neither ResNet18's nor ResNet34's: " + "; ".join(why))
+    read = {k: v for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+    return match_net(read, [(net, label, shapes(net)) for net, label in ((_lib.TQ_NET_RESNET18, "ResNet18"), (_lib.TQ_NET_RESNET34, "ResNet34"))])
 
 
 def _layer_stride(conv):
@@ -143,7 +131,7 @@ class ResNet34(_ResNet):
     NET = _lib.TQ_NET_RESNET34
 
 
-class ResNetForward(Handle):
+class ResNetForward(ForwardHandle):
     """ResNet18's or ResNet34's forward pass as HIP kernels (tq_resnet_*; numerics contract in include/toricenv.h): bf16
     weights and activations, f32 accumulation, BatchNorm folded to an f32 scale and shift, f32 Q-values.  It is the
     EVAL-MODE network -- BatchNorm with its running statistics, what ``model.eval()`` computes under ``no_grad`` in the
@@ -158,20 +146,12 @@ class ResNetForward(Handle):
     One handle, one stream: calls share the handle's activation scratch, 4 x max_rows x d^2 x 512 bytes (0.68 GB at d = 9,
     3.7 GB at d = 21 with the default of 4096 rows; a larger call is walked in passes of ``max_rows``)."""
 
-    any_rows = True
-    gathers = False
-    _destroy = "tq_resnet_destroy"
+    _create, _forward, _destroy = "tq_resnet_create", "tq_resnet_forward", "tq_resnet_destroy"
 
     def __init__(self, model_or_state_dict, system_size, device, max_rows=1 << 12, eps=1e-5):
-        self.system_size = int(system_size)
         self.eps = float(eps)
-        sd = self._state_dict(model_or_state_dict)
-        self.net = which_net(sd)
-        self.device = require_gpu(device)
-        self._L = _lib.load()
-        self._h = C.c_void_p(None)
-        check(self._L.tq_resnet_create(C.byref(self._h), self.net, self.system_size, int(max_rows), self.device.index))
-        self.load(model_or_state_dict)
+        self.net = which_net(self._state_dict(model_or_state_dict))  # a wrong net is refused before the device is asked for
+        super().__init__(model_or_state_dict, system_size, device, max_rows, self.net)
 
     def _state_dict(self, model_or_state_dict):
         if not hasattr(model_or_state_dict, "state_dict"):
@@ -192,23 +172,5 @@ class ResNetForward(Handle):
         w = [dev(conv + ".weight") for conv, _, _ in convs(net)]
         bn = [dev(f"{b}.{k}") for _, b, _ in convs(net) for k in BN_KEYS]
         lw, lb = dev("linear.weight"), dev("linear.bias")
-        ptrs = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
-        self._call(self._L.tq_resnet_load, ptrs(w), ptrs(bn), _ptr(lw), _ptr(lb), self.eps)    # the pack kernel reads them on the
-        return self                                                 # current stream, where copies made above are freed in stream order
-
-    def __call__(self, persp):
-        persp, dtype = _check_stack(persp, self.system_size, self.device, "stack")
-        q = torch.empty((persp.shape[0], 3), dtype=torch.float32, device=self.device)
-        self._call(self._L.tq_resnet_forward, _ptr(persp), dtype, persp.shape[0], _ptr(q))
-        return q
-
-    forward = __call__
-
-    def eval(self):
-        return self
-
-    def train(self, mode=True):
-        return self
-
-    def to(self, *args, **kwargs):                         # evaluate() moves its model to the device: it is there already
-        return self
+        self._call(self._L.tq_resnet_load, _pointers(w), _pointers(bn), _ptr(lw), _ptr(lb), self.eps)   # the pack kernel reads them
+        return self                                       # on the current stream, where copies made above are freed in stream order
