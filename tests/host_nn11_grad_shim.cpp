@@ -1,10 +1,11 @@
 // Host-side instantiation of the product's NN_11 learner-step headers (csrc/nn11.hpp, csrc/nn11_grad.hpp), beside
 // host_nn11_shim.cpp: torch-layout weights are packed with the headers' own pack routines (forward and dgrad images), and
-// the scalar forward of host_nn11_ref.hpp, a head and a backward under the numerics contract of include/toricenv.h read
-// the images, the activation and gradient images and the tap -> source pixel maps ONLY through the headers' index
-// functions -- what the pack kernels, the MFMA kernels and the head kernel use on the device.
+// the scalar forward of host_conv_ref.hpp, a head and a backward (its dgrad: that header's conv_host under the ReLU mask)
+// under the numerics contract of include/toricenv.h read the images, the activation and gradient images and the tap ->
+// source pixel maps ONLY through the headers' index functions -- what the pack kernels, the MFMA kernels and the head
+// kernel use on the device.
 // TEST ONLY: built by tests/test_nn11_grad_host.py into a temp dir with g++; it is not a backend of the product.
-#include "host_nn11_ref.hpp"
+#include "host_conv_ref.hpp"
 #include "nn11_grad.hpp"
 
 using namespace tq;
@@ -17,7 +18,7 @@ extern "C" int shim_nn11_grad(int d, const float* const* weights, const float* c
     if (!size_ok(d) || n < 1) return -1;
     constexpr int L = NN11_LAYERS;
     const int pix = d * d, npix = nn11_out_pixels(d);
-    const PackedNet net(d, weights, biases);
+    const PackedNet net = nn11_packed(d, weights, biases);
     const std::vector<float>& limg = net.limg;
     std::vector<float> dt[L + 1];
     for (int l = 2; l <= L; ++l) {
@@ -33,7 +34,7 @@ extern "C" int shim_nn11_grad(int d, const float* const* weights, const float* c
     for (int i = 0; i < n; ++i) {
         uint16_t* mine[L + 1] = {nullptr};                                  // record i's part of every image
         for (int l = 1; l <= L; ++l) mine[l] = act[l].data() + nn11_act_index(i, 0, 0, nn11_layer_pixels(l, d), nn11_cpad(nn11_cout(l)));
-        forward_one(d, net, stack + (size_t)i * 2 * pix, mine, q + i * NN11_OUT);
+        forward_one<NN11_MAX_CP>(d, net, stack + (size_t)i * 2 * pix, mine, q + i * NN11_OUT);
     }
 
     // ---- head
@@ -100,24 +101,10 @@ extern "C" int shim_nn11_grad(int d, const float* const* weights, const float* c
         const int dmode = l == L ? NN11_FULL : NN11_ZERO;
 #pragma omp parallel for schedule(dynamic, 1)
         for (int i = 0; i < n; ++i) {
-            std::vector<float> acc(NN11_MAX_CP);
-            for (int o = 0; o < pix; ++o) {
-                for (int c = 0; c < cpi; ++c) acc[c] = 0.f;
-                for (int tap = 0; tap < 9; ++tap) {
-                    const int sp = nn11_src_pixel(dmode, d, o / d, o % d, tap);
-                    if (sp < 0) continue;
-                    for (int k = 0; k < cpo; ++k) {
-                        const float gv = nn11_f32(g[nn11_act_index(i, sp, k, opix, cpo)]);
-                        if (gv == 0.f) continue;
-                        const float* ww = dt[l].data() + ((size_t)tap * cpo + k) * cpi;
-                        for (int c = 0; c < cpi; ++c) acc[c] += gv * ww[c];
-                    }
-                }
-                for (int c = 0; c < cpi; ++c) {
-                    const int64_t e = nn11_act_index(i, o, c, pix, cpi);
-                    gn[e] = nn11_mask(act[l - 1][e]) ? nn11_bf16(acc[c]) : (uint16_t)0;
-                }
-            }
+            const uint16_t* mask = act[l - 1].data() + nn11_act_index(i, 0, 0, pix, cpi);
+            conv_host<NN11_MAX_CP>(dt[l].data(), 9, nn11_dksteps(l), nn11_dntiles(l), d, opix, nullptr, g.data() + nn11_act_index(i, 0, 0, opix, cpo),
+                      [&](int oy, int ox, int tap) { return nn11_src_pixel(dmode, d, oy, ox, tap); },
+                      [&](float sum, int, int64_t at) { return nn11_mask(mask[at]) ? sum : 0.f; }, gn.data() + nn11_act_index(i, 0, 0, pix, cpi));
         }
         g.swap(gn);
     }

@@ -1,7 +1,7 @@
 // Host-side instantiation of the product's NN_11 header (csrc/nn11.hpp), beside host_td_target_shim.cpp: torch-layout
-// weights are packed with the header's own pack routines, and the scalar forward of host_nn11_ref.hpp runs over them.
+// weights are packed with the header's own pack routines, and the scalar forward of host_conv_ref.hpp runs over them.
 // TEST ONLY: built by tests/test_nn11_host.py into a temp dir with g++; it is not a backend of the product.
-#include "host_nn11_ref.hpp"
+#include "host_conv_ref.hpp"
 
 using namespace tq;
 
@@ -9,13 +9,13 @@ using namespace tq;
 extern "C" int shim_nn11_forward(int d, const float* const* weights, const float* const* biases, const uint8_t* stack,
                                  int64_t P, float* q) {
     if (!size_ok(d)) return -1;
-    const PackedNet net(d, weights, biases);
+    const PackedNet net = nn11_packed(d, weights, biases);
 #pragma omp parallel for schedule(dynamic, 4)
     for (int64_t p = 0; p < P; ++p) {
         std::vector<uint16_t> buf[2] = {std::vector<uint16_t>((size_t)d * d * NN11_MAX_CP), std::vector<uint16_t>((size_t)d * d * NN11_MAX_CP)};
         uint16_t* act[NN11_LAYERS + 1];
         for (int l = 0; l <= NN11_LAYERS; ++l) act[l] = buf[l & 1].data();
-        forward_one(d, net, stack + p * 2 * d * d, act, q + p * NN11_OUT);
+        forward_one<NN11_MAX_CP>(d, net, stack + p * 2 * d * d, act, q + p * NN11_OUT);
     }
     return 0;
 }

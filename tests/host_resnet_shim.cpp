@@ -1,9 +1,8 @@
 // Host-side instantiation of the ResNets' header (csrc/resnet.hpp), beside host_nnw_shim.cpp: the network table, the
 // index functions, the BatchNorm fold and the host pack routines as the pack kernel and the conv kernel use them, and one
-// scalar forward under the numerics contract of include/toricenv.h that reads the packed images ONLY through those index
-// functions.  TEST ONLY: built by tests/test_resnet_host.py into a temp dir with g++; it is not a backend of the product.
-#include <vector>
-
+// scalar forward under the numerics contract of include/toricenv.h over the scalar convolution of host_conv_ref.hpp.
+// TEST ONLY: built by tests/test_resnet_host.py into a temp dir with g++; it is not a backend of the product.
+#include "host_conv_ref.hpp"
 #include "resnet.hpp"
 
 using namespace tq;
@@ -38,37 +37,8 @@ extern "C" void shim_resnet_pack_conv(int cin, int cout, int taps, const float* 
 extern "C" void shim_resnet_pack_linear(const float* w, float* limg) { resnet_pack_linear_host(w, limg); }
 
 namespace {
-struct Packed { std::vector<uint16_t> img; std::vector<float> scale, shift; };
-
-// one convolution of one perspective: in [side^2][16 ks] (or the u8 stack [2][side][side]) -> out [opix][32 nt].  Sums
-// within a pixel tap by tap, k ascending; then acc s + t, the residual, the ReLU and RNE to bf16.
-void conv_host(const ResConv& c, int side, const Packed& p, const uint16_t* in, const uint8_t* stack, int epi, const uint16_t* res,
-               uint16_t* out) {
-    const int ks = resnet_ksteps(c.cin), nt = resnet_ntiles(c.cout), cpo = nt * 32, cpi = ks * 16;
-    const int os = c.stride == 2 ? resnet_half(side) : side, opix = os * os, pix = side * side;
-    std::vector<float> acc(cpo);
-    for (int o = 0; o < opix; ++o) {
-        for (int ch = 0; ch < cpo; ++ch) acc[ch] = 0.f;
-        for (int tap = 0; tap < c.taps; ++tap) {
-            const int sp = resnet_src_pixel(side, c.stride, c.taps, o / os, o % os, tap);
-            if (sp < 0) continue;                                   // the zero padding
-            for (int k = 0; k < (stack ? 2 : cpi); ++k) {
-                const float a = stack ? nn11_f32(nn11_bf16((float)stack[k * pix + sp])) : nn11_f32(in[nn11_act_index(0, sp, k, pix, cpi)]);
-                if (a == 0.f) continue;                             // adds +0: the sum is the same without it
-                for (int ch = 0; ch < cpo; ++ch)
-                    acc[ch] += a * nn11_f32(p.img[stack ? nn11_wimg_of(ch, nn11_k1(k, tap), 0, ks, nt) : nn11_wimg_of(ch, k, tap, ks, nt)]);
-            }
-        }
-        for (int ch = 0; ch < cpo; ++ch) {
-            const int64_t at = nn11_act_index(0, o, ch, opix, cpo);
-            float v = acc[ch] * p.scale[ch] + p.shift[ch];
-            if (epi == RESNET_EPI_ADD_RELU) v = v + nn11_f32(res[at]);
-            if (epi != RESNET_EPI_NONE) v = v > 0.f ? v : 0.f;
-            out[at] = nn11_bf16(v);
-        }
-    }
+struct Packed { std::vector<float> wt, scale, shift; };      // one convolution; wt: the packed image, expanded
 }
-}  // namespace
 
 // conv_weights[n], bn[4 n] (gamma, beta, mean, var per convolution), lin_w [3][512], lin_b [3]: host pointers in torch
 // layout; stack u8 [P][2][d][d] -> q f32 [P][3].  The block schedule is abi_resnet.hpp's and the head's order of sums is
@@ -81,11 +51,12 @@ extern "C" int shim_resnet_forward(int net, int d, const float* const* conv_weig
     std::vector<Packed> pk(n);
     for (int i = 0; i < n; ++i) {
         const ResConv c = resnet_conv(s, i);
-        pk[i].img.resize(resnet_wimg_elems(c.cin, c.cout, c.taps));
+        std::vector<uint16_t> img(conv_wimg_elems(c.cin, c.cout, c.taps));
         pk[i].scale.resize(nn11_cpad(c.cout));
         pk[i].shift.resize(nn11_cpad(c.cout));
         resnet_pack_conv_host(c.cin, c.cout, c.taps, conv_weights[i], bn[4 * i], bn[4 * i + 1], bn[4 * i + 2], bn[4 * i + 3], eps,
-                              pk[i].img.data(), pk[i].scale.data(), pk[i].shift.data());
+                              img.data(), pk[i].scale.data(), pk[i].shift.data());
+        pk[i].wt = expand(img, conv_img_taps(c.cin, c.taps), conv_ksteps(c.cin), conv_ntiles(c.cout));
     }
     std::vector<float> limg(resnet_lin_elems());
     resnet_pack_linear_host(lin_w, limg.data());
@@ -93,9 +64,19 @@ extern "C" int shim_resnet_forward(int net, int d, const float* const* conv_weig
     for (int64_t p = 0; p < P; ++p) {
         std::vector<uint16_t> act[4];
         for (auto& a : act) a.assign((size_t)pix * RESNET_MAX_CP, 0);
+        // convolution i: in [side^2][16 ks] (or the u8 stack [2][side][side]) -> out [opix][32 nt]; the epilogue: acc s + t,
+        // the residual, the ReLU
         auto run = [&](int i, const uint16_t* in, const uint8_t* st, int epi, const uint16_t* res, uint16_t* out) {
             const ResConv c = resnet_conv(s, i);
-            conv_host(c, c.half_in ? hs : d, pk[i], in, st, epi, res, out);
+            const int side = c.half_in ? hs : d;
+            conv_host<RESNET_PLANES[RESNET_STAGES - 1]>(pk[i].wt.data(), c.taps, conv_ksteps(c.cin), conv_ntiles(c.cout), c.stride == 2 ? resnet_half(side) : side,
+                      side * side, st, in, [&](int y, int x, int tap) { return resnet_src_pixel(side, c.stride, c.taps, y, x, tap); },
+                      [&](float sum, int ch, int64_t at) {
+                          float v = sum * pk[i].scale[ch] + pk[i].shift[ch];
+                          if (epi == RESNET_EPI_ADD_RELU) v = v + nn11_f32(res[at]);
+                          if (epi != RESNET_EPI_NONE) v = v > 0.f ? v : 0.f;
+                          return v;
+                      }, out);
         };
         run(0, nullptr, stack + p * 2 * pix, RESNET_EPI_RELU, nullptr, act[0].data());
         int x = 0;

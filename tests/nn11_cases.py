@@ -1,48 +1,27 @@
-"""Inputs and yardsticks shared by tests/test_nn11_host.py and tests/test_gpu_nn11.py (not a test module).
-
-  integer_state_dict   weights under which every activation of NN_11 is a small integer, so that a bf16 / f32-accumulate
-                       forward must equal torch's f32 forward bit for bit
-  stack_of             the oracle's perspectives of n lattices reset at p = 0.1
-  contract_forward     the numerics contract of include/toricenv.h restated in torch ops: the yardstick for trained weights
-  exact_dense_case     a network with dense layers and real bf16 roundings (ties included) whose every f32 sum is
-                       exact, and its Q-table by dense_reference, a float64 forward of the contract with switches for
-                       the ways a kernel can be subtly wrong (MUTANTS)
-"""
+"""Inputs and yardsticks shared by tests/test_nn11_host.py and tests/test_gpu_nn11.py (not a test module):
+tests/plain_cases.py bound to NN_11, and what only NN_11 has (a trained checkpoint, the stack-conversion cases)."""
 import os
 
-import numpy as np
-import torch
-import torch.nn.functional as F
-
 import toric_rl_decoder_amd as T
-from oracle import toric_oracle as O
 
+import plain_cases as P
+from plain_cases import (CASE_LIMIT, EXACT_LIMIT, MUTANTS, SPARSE_TAPS, TIES, U8_VALUES, WIDE_SHARE,  # noqa: F401
+                         WIDE_VALUES, alive_quantile, contract_forward, dense_reference, dense_rows, dense_rows_for,
+                         greedy_per_lattice, group, layer_outputs, rms, round_bf16, stack_of, wide_stack)
+
+NET = P.Plain(11, T.NN_11, integer_seed=lambda d: 11000 + d, dense_seed=lambda d, l: [1100, d, l], sparse=P.sparse_by_row,
+              centre_d3=False, alive_conv1=False)
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SIZES = tuple(T.SUPPORTED_SIZES)
-CH = T.NN_11.CHANNELS
-NAMES = [f"conv{i + 1}" for i in range(11)] + ["linear1"]
+CH = NET.ch
+NAMES = NET.names
 PARAMS = [f"{n}.{k}" for n in NAMES for k in ("weight", "bias")]        # the 24 tensors, in model.parameters() order
+DENSE_LAYERS = tuple(range(2, 12))
+WIDE_CASES = ((7, 2), (7, 6), (7, 11), (13, 8))       # (d, dense_layer) of the stack-conversion tests
 
 
 def integer_state_dict(d):
-    """Seeded by d.  Every output channel of every conv: +1 at one random (input channel, tap) and, with probability
-    1/2, -1 at another; biases 1 with probability 1/4, else 0; linear weights integers in [-8, 8]; linear bias integers
-    in [-3, 3]."""
-    rng = np.random.default_rng(11000 + d)
-    sd = {}
-    for i in range(11):
-        cin, cout = CH[i], CH[i + 1]
-        w = np.zeros((cout, cin * 9), np.float32)
-        for o in range(cout):
-            a, b = rng.choice(cin * 9, 2, replace=False)
-            w[o, a] = 1
-            if rng.random() < 0.5:
-                w[o, b] = -1
-        sd[f"conv{i + 1}.weight"] = torch.from_numpy(w.reshape(cout, cin, 3, 3))
-        sd[f"conv{i + 1}.bias"] = torch.from_numpy((rng.random(cout) < 0.25).astype(np.float32))
-    sd["linear1.weight"] = torch.from_numpy(rng.integers(-8, 9, (3, 64 * (d - 2) ** 2)).astype(np.float32))
-    sd["linear1.bias"] = torch.from_numpy(rng.integers(-3, 4, 3).astype(np.float32))
-    return sd
+    return P.integer_state_dict(NET, d)
 
 
 def trained_state_dict(d):
@@ -51,251 +30,12 @@ def trained_state_dict(d):
 
 
 def model_of(sd, d):
-    m = T.NN_11(d)
-    m.load_state_dict(sd)
-    return m.eval()
-
-
-def stack_of(d, n, seed=7):
-    """-> (perspectives (P,2,d,d) uint8, offsets (n+1,) int64) of n lattices reset at p = 0.1."""
-    _, st = O.reset_lattices(seed + d, np.arange(n), 0, 0.1, d)
-    per, _, _, off = O.generate_perspective_batch(st)
-    return np.ascontiguousarray(per, np.uint8), off
-
-
-def layer_outputs(model, x):
-    """torch's own forward, layer by layer -> (list of the eleven post-ReLU activations, q)."""
-    outs = []
-    with torch.no_grad():
-        x = F.pad(x, (1, 1, 1, 1), mode="circular")
-        for i in range(11):
-            x = F.relu(getattr(model, f"conv{i + 1}")(x))
-            outs.append(x)
-        return outs, model.linear1(x.flatten(1))
-
-
-def _r(t):
-    return t.bfloat16().float()
-
-
-def contract_forward(model, x):
-    """The contract in torch ops: weights .bfloat16().float(), f32 conv2d, .bfloat16().float() after each ReLU, an f32
-    linear on rounded weights; biases f32."""
-    with torch.no_grad():
-        x = F.pad(_r(x.float()), (1, 1, 1, 1), mode="circular")
-        for i in range(11):
-            c = getattr(model, f"conv{i + 1}")
-            x = _r(F.relu(F.conv2d(x, _r(c.weight), c.bias, padding=c.padding)))
-        return F.linear(x.flatten(1), _r(model.linear1.weight), model.linear1.bias)
-
-
-def rms(a, b):
-    return float(torch.sqrt(torch.mean((a.double() - b.double()) ** 2)))
-
-
-def greedy_per_lattice(q, off):
-    """first maximum over each lattice's (count, 3) slice, as a flat index into the slice."""
-    q = q.detach().cpu().numpy()
-    return np.array([int(np.argmax(q[off[i]:off[i + 1]].reshape(-1))) for i in range(len(off) - 1)])
-
-
-# ---- the dense exact case -------------------------------------------------------------------------------------------
-# Every term of every sum is an integer and the sum of the terms' magnitudes (the bias included) stays below 2^24, so
-# every partial sum in any order is an integer that f32 holds: whatever order a kernel sums in, it gets the one f32
-# value, and the bf16 rounding after it is a function of that value.  Bit equality may then be demanded of a network
-# that is dense and rounds.
-TIES = (257, 259, 261, 263)                   # integers bf16 cannot hold, each half-way: RNE -> 256, 260, 260, 264
-EXACT_LIMIT = float(1 << 24)
-CASE_LIMIT = float(1 << 23)                    # what exact_dense_case keeps to: a factor 2 below the limit
-DENSE_LAYERS = tuple(range(2, 12))
-SPARSE_TAPS = 4                               # non-zero weights per output channel of a conv layer that is not dense
-
-
-def alive_quantile(d):
-    """A channel's bias is -ceil of this quantile of its pre-activation.  0.9 keeps a tenth of the activations alive and
-    the sums within the limit; d = 3 has nine pixels, and one in ten of them alive carries a change made in one layer to
-    Q in too few rows, so it keeps a quarter alive (its sums are the smallest of all sizes)."""
-    return 0.75 if d == 3 else 0.9
-
-
-# switches of dense_reference: each a way a kernel can be wrong that the dense case must see (tests/test_nn11_host.py)
-MUTANTS = {
-    "activations truncated": dict(act_round="trunc"),
-    "activations rounded half-up": dict(act_round="half_up"),
-    "weights truncated": dict(weight_round="trunc"),
-    "bias after the ReLU": dict(bias_after_relu=True),
-    "circular padding in the dense layer": dict(circular_dense=True),
-    "taps of the dense layer transposed": dict(transpose_dense=True),
-    "last input channel of the dense layer dropped": dict(drop_last_cin_dense=True),
-}
+    return P.model_of(NET, sd, d)
 
 
 def mutant_is_void(name, d, dense_layer):
-    """conv11 has no padding to get wrong; at d = 3 the padding variant is exempt as well."""
-    return name == "circular padding in the dense layer" and (dense_layer == 11 or d == 3)
-
-
-def round_bf16(t, mode="rne", exact=True):
-    """f64 tensor -> its values rounded to bf16, as f64; ``exact`` asserts that f32 holds them all (a mutant's need
-    not).  rne: torch's own conversion; trunc: toward zero; half_up: the magnitude's half goes up."""
-    f = t.float()
-    assert not exact or torch.equal(f.double(), t), "a value that f32 does not hold"
-    if mode == "rne":
-        return f.bfloat16().double()
-    u = f.view(torch.int32)
-    if mode == "half_up":
-        u = u + 0x8000
-    return (u & ~0xFFFF).view(torch.float32).double()
-
-
-def dense_reference(sd, x, dense_layer, act_round="rne", weight_round="rne", bias_after_relu=False, circular_dense=False,
-                    transpose_dense=False, drop_last_cin_dense=False, stack_round="rne", fit_bias=False, limit=EXACT_LIMIT):
-    """The contract of include/toricenv.h in float64, in plain torch ops: stack elements and weights rounded to bf16,
-    f64 convolutions under the three paddings, + bias, ReLU, rounded to bf16; an f64 linear layer on rounded weights.
-    ``x``: (rows, 2, d, d) tensor of any dtype.  -> (q f64 (rows, 3), stats).
-
-    Asserts for every output of every layer that sum |w a| + |bias| < ``limit``: at 2^24 the exactness condition
-    (exact_dense_case passes None to measure the sums while it fits a case, and then holds them to CASE_LIMIT).
-    fit_bias: set each conv bias in ``sd`` to -ceil(alive_quantile(d) quantile of the channel's pre-activation over all
-    rows and pixels), layer by layer, before it is used.
-    The other switches (MUTANTS, and stack_round for the stack's conversion) make a forward that is wrong on purpose; the
-    condition does not apply to its sums."""
-    mutant = (act_round != "rne" or weight_round != "rne" or stack_round != "rne" or bias_after_relu or circular_dense
-              or transpose_dense or drop_last_cin_dense)
-    assert not (mutant and fit_bias)
-    check, exact = not mutant, not mutant and limit is not None
-    a = round_bf16(x.double(), stack_round)
-    a = F.pad(a, (1, 1, 1, 1), mode="circular")
-    stats = {"conv_sum": 0.0, "changed": [], "alive": []}
-    for l in range(1, 12):
-        w = sd[f"conv{l}.weight"].double()
-        pad = 0 if l in (1, 11) else 1
-        if l == dense_layer:
-            if transpose_dense:
-                w = w.transpose(2, 3)
-            if drop_last_cin_dense:
-                w = w.clone()
-                w[:, -1] = 0
-            if circular_dense and pad:
-                a, pad = F.pad(a, (1, 1, 1, 1), mode="circular"), 0
-        w = round_bf16(w, weight_round, exact)
-        pre = F.conv2d(a, w, None, padding=pad)
-        if fit_bias:
-            qu = torch.quantile(pre.transpose(0, 1).flatten(1), alive_quantile(x.shape[-1]), dim=1)
-            sd[f"conv{l}.bias"] = (-torch.ceil(qu)).float()
-        b = sd[f"conv{l}.bias"].double()[None, :, None, None]
-        if check:
-            mag = float((F.conv2d(a.abs(), w.abs(), None, padding=pad) + b.abs()).max())
-            assert limit is None or mag < limit, (l, mag)
-            stats["conv_sum"] = max(stats["conv_sum"], mag)
-        y = F.relu(pre) + b if bias_after_relu else F.relu(pre + b)
-        a = round_bf16(y, act_round, exact)
-        stats["changed"].append(float((a != y).double().mean()))
-        stats["alive"].append(float((a > 0).double().mean()))
-    feat = a.flatten(1)
-    lw = round_bf16(sd["linear1.weight"].double(), weight_round, exact)
-    lb = sd["linear1.bias"].double()
-    if check:
-        mag = float((feat.abs() @ lw.abs().T + lb.abs()).max())
-        assert limit is None or mag < limit, ("linear1", mag)
-        stats["linear_sum"] = mag
-    stats["distinct_features"] = len({r.tobytes() for r in feat.numpy()}) / feat.shape[0]
-    return feat @ lw.T + lb, stats
-
-
-def _tie(rng, size=None):
-    return rng.choice(TIES, size) * rng.choice((-1, 1), size)
-
-
-def _dense_state_dict(d, dense_layer, dense_mag, linear_mag, unit_layers, ties=True):
-    """Seeded by (d, dense_layer); the conv biases are still to be fitted."""
-    rng = np.random.default_rng([1100, d, dense_layer])
-    sd = {}
-    w = rng.integers(-1, 2, (CH[1], 18)).astype(np.float64)              # conv1: dense in {-1, 0, 1} ...
-    for i, o in enumerate(range(0, CH[1], 8) if ties else ()):            # ... with a tie in every eighth channel: each
-        w[o, rng.integers(18)] = TIES[i % 4] * (1 - (i // 4) % 2 * 2)     # of TIES twice with either sign
-    sd["conv1.weight"] = torch.from_numpy(w.reshape(CH[1], 2, 3, 3)).float()
-    for l in range(2, 12):
-        cin, cout = CH[l - 1], CH[l]
-        if l == dense_layer:
-            w = rng.choice([-2, -1, 1, 2][2 - dense_mag:2 + dense_mag], (cout, cin * 9)).astype(np.float64)
-        else:
-            w, mag = np.zeros((cout, cin * 9)), 1 if l > 11 - unit_layers else 2
-            for o in range(cout):
-                w[o, rng.choice(cin * 9, SPARSE_TAPS, replace=False)] = rng.choice([-2, -1, 1, 2][2 - mag:2 + mag], SPARSE_TAPS)
-            if l == dense_layer - 1:                                      # the dense layer's last input channel is alive
-                w[-1] = rng.choice([-2, -1, 1, 2], cin * 9)
-        sd[f"conv{l}.weight"] = torch.from_numpy(w.reshape(cout, cin, 3, 3)).float()
-    lw = rng.integers(-linear_mag, linear_mag + 1, (3, 64 * (d - 2) ** 2)).astype(np.float64)
-    if ties:
-        lw[:, ::97] = _tie(rng, lw[:, ::97].shape)
-    sd["linear1.weight"] = torch.from_numpy(lw).float()
-    sd["linear1.bias"] = torch.from_numpy(rng.integers(-3, 4, 3).astype(np.float32))
-    for l in range(1, 12):
-        sd[f"conv{l}.bias"] = torch.zeros(CH[l])
-    return sd
-
-
-_stacks, _dense = {}, {}
-WIDE_VALUES = (2, 3) + TIES                    # stack elements beside 0 and 1 that a f32 / f16 stack is given
-U8_VALUES = (2, 255)                           # ... and a u8 stack (bf16 holds them)
-WIDE_SHARE = 0.1                              # of the stack's elements; the rest stay the perspective's 0 / 1
-WIDE_CASES = ((7, 2), (7, 6), (7, 11), (13, 8))       # (d, dense_layer) of the stack-conversion tests
-
-
-def dense_rows(d, rows):
-    """the first ``rows`` perspectives of stack_of(d, ...), uint8"""
-    n = 64
-    while d not in _stacks or _stacks[d].shape[0] < rows:
-        _stacks[d] = stack_of(d, n)[0]
-        n *= 2
-    return _stacks[d][:rows]
-
-
-def wide_stack(d, rows, values):
-    """dense_rows(d, rows) as f32 with WIDE_SHARE of its elements replaced by draws from ``values``."""
-    rng = np.random.default_rng([1101, d, len(values)])
-    x = dense_rows(d, rows).astype(np.float32)
-    m = rng.random(x.shape) < WIDE_SHARE
-    x[m] = rng.choice(values, int(m.sum()))
-    return x
+    return P.mutant_is_void(NET, name, d, dense_layer)
 
 
 def exact_dense_case(d, dense_layer, rows, values=None):
-    """-> (state_dict, stack (rows, 2, d, d) numpy, Q-table f32 (rows, 3) numpy, stats of dense_reference).
-    The stack: dense_rows(d, rows), uint8; with ``values``, wide_stack(d, rows, values), f32.
-    conv1 dense in {-1, 0, 1} with a TIES weight in every eighth output channel; layer ``dense_layer`` dense in
-    {-2, -1, 1, 2}; SPARSE_TAPS such weights per output channel elsewhere; conv biases fitted to this stack
-    (dense_reference's fit_bias), which keeps a tenth of the activations alive and the sums from growing; linear1 dense
-    integers in [-2, 2] with a TIES weight in every 97th column.  Where a sum's magnitude would reach CASE_LIMIT, first
-    linear1 is narrowed to [-1, 1], then the dense layer to +-1, then the last k layers' weights to +-1, k = 1, 2, ...
-    With ``values`` the weights hold no TIES and every layer is narrowed at once: an element of 263 under a weight of
-    263 is 69169 after conv1, and one such feature under a TIES weight of linear1 would spend the limit by itself; the
-    stack's elements bring the roundings there.  The two most recent cases are kept."""
-    key = (d, dense_layer, rows, values)
-    if key not in _dense:
-        x = torch.from_numpy(dense_rows(d, rows) if values is None else wide_stack(d, rows, values))
-        steps = ((2, 2, 0), (2, 1, 0)) + tuple((1, 1, k) for k in range(11)) if values is None else ((1, 1, 10),)
-        for narrowed in steps:
-            sd = _dense_state_dict(d, dense_layer, *narrowed, ties=values is None)
-            _, stats = dense_reference(sd, x, dense_layer, fit_bias=True, limit=None)
-            if max(stats["conv_sum"], stats["linear_sum"]) < CASE_LIMIT:
-                break
-        q, stats = dense_reference(sd, x, dense_layer, limit=CASE_LIMIT)       # the fitted network, held to the condition
-        stats["narrowed"] = narrowed
-        q32 = q.float()
-        assert torch.equal(q32.double(), q)
-        while len(_dense) >= 2:
-            del _dense[next(iter(_dense))]
-        _dense[key] = (sd, x.numpy(), q32.numpy(), stats)
-    return _dense[key]
-
-
-def group(d):
-    return max(1, 256 // (d * d))              # perspectives per workgroup: NN11Geom<D>::G of csrc/nn11.hpp
-
-
-def dense_rows_for(d):
-    """the row count of the dense case at size d: 2 G + 3 perspectives cross the tile, workgroup and pass edges of a
-    handle of G + 1 rows"""
-    return 2 * group(d) + 3
+    return P.exact_dense_case(NET, d, dense_layer, rows, values)

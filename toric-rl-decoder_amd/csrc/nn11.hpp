@@ -124,6 +124,16 @@ TQ_HD float conv_wimg_value(int cin, int cout, int taps, int64_t idx, const floa
     return w[((int64_t)c.cout * cin + c.k) * 9 + c.tap];
 }
 TQ_HD float nn11_wimg_value(int l, int64_t idx, const float* w) { return conv_wimg_value(nn11_cin(l), nn11_cout(l), 9, idx, w); }
+// host-side pack of one convolution by its channel counts, for the unit tests: the weight image; with it the padded bias
+inline void conv_pack_image_host(int cin, int cout, int taps, const float* w, uint16_t* wimg) {
+    const int64_t n = conv_wimg_elems(cin, cout, taps);
+    for (int64_t i = 0; i < n; ++i) wimg[i] = nn11_bf16(conv_wimg_value(cin, cout, taps, i, w));
+}
+inline void conv_pack_layer_host(int cin, int cout, int taps, const float* w, const float* b, uint16_t* wimg, float* bias) {
+    conv_pack_image_host(cin, cout, taps, w, wimg);
+    const int cp = nn11_cpad(cout);
+    for (int c = 0; c < cp; ++c) bias[c] = c < cout ? b[c] : 0.f;
+}
 
 // ---- dgrad weight image of layer l = 2..11: the image of the convolution that takes G_l (cout(l) channels) to the
 // gradient of layer l - 1's output (cin(l) channels).  Same fragment order with the two channel counts in each other's
@@ -190,10 +200,7 @@ inline int nn11_group(int d) { const int g = 256 / (d * d); return g > 0 ? g : 1
 
 // ---- host-side pack (what k_nn11_pack does on the device), for the header's unit test
 inline void nn11_pack_layer_host(int l, const float* w, const float* b, uint16_t* wimg, float* bias) {
-    const int64_t n = nn11_wimg_elems(l);
-    for (int64_t i = 0; i < n; ++i) wimg[i] = nn11_bf16(nn11_wimg_value(l, i, w));
-    const int cp = nn11_cpad(nn11_cout(l));
-    for (int c = 0; c < cp; ++c) bias[c] = c < nn11_cout(l) ? b[c] : 0.f;
+    conv_pack_layer_host(nn11_cin(l), nn11_cout(l), 9, w, b, wimg, bias);
 }
 inline void nn11_pack_dgrad_host(int l, const float* w, uint16_t* dimg) {       // l = 2..11
     const int64_t n = nn11_dimg_elems(l);

@@ -65,10 +65,7 @@ TQ_HD float nnw_lin_value(int64_t idx, int npix, const float* w) {
 
 // ---- host-side pack (what k_nnw_pack does on the device), for the header's unit test
 inline void nnw_pack_layer_host(int cin, int cout, const float* w, const float* b, uint16_t* wimg, float* bias) {
-    const int64_t n = conv_wimg_elems(cin, cout, 9);
-    for (int64_t i = 0; i < n; ++i) wimg[i] = nn11_bf16(conv_wimg_value(cin, cout, 9, i, w));
-    const int cp = nn11_cpad(cout);
-    for (int c = 0; c < cp; ++c) bias[c] = c < cout ? b[c] : 0.f;
+    conv_pack_layer_host(cin, cout, 9, w, b, wimg, bias);
 }
 inline void nnw_pack_linear_host(int d, const float* w, float* limg) {
     const int64_t n = nnw_lin_elems(d);

@@ -115,8 +115,7 @@ TQ_HD float resnet_lin_value(int64_t idx, const float* w) { return nn11_f32(nn11
 // ---- host-side pack (what k_resnet_pack does on the device), for the header's unit test
 inline void resnet_pack_conv_host(int cin, int cout, int taps, const float* w, const float* gamma, const float* beta, const float* mean,
                                   const float* var, float eps, uint16_t* wimg, float* scale, float* shift) {
-    const int64_t n = conv_wimg_elems(cin, cout, taps);
-    for (int64_t i = 0; i < n; ++i) wimg[i] = nn11_bf16(conv_wimg_value(cin, cout, taps, i, w));
+    conv_pack_image_host(cin, cout, taps, w, wimg);
     const int cp = nn11_cpad(cout);
     for (int c = 0; c < cp; ++c) {
         const ResFold f = c < cout ? resnet_fold(gamma[c], beta[c], mean[c], var[c], eps) : ResFold{0.f, 0.f};
