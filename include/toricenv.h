@@ -535,13 +535,14 @@ int tq_nn11_grad_opt_step(tq_nn11_grad* h, int kind, double lr, double beta1, do
                           const float* const* grad_b, float* const* m_w, float* const* m_b, float* const* v_w,
                           float* const* v_b, void* stream);
 
-/* ---- The forward pass of the reference's two wide Q-networks on the device (src/nn/torch/NN.py:47-133), forward only:
+/* ---- The forward pass of the reference's two wide Q-networks on the device (src/nn/torch/NN.py:47-133):
  *   TQ_NET_NN8   NN_8:  8 conv3x3 + ReLU, channels 2-256-256-240-224-220-215-205-200
  *   TQ_NET_NN17  NN_17: 20 conv3x3 + ReLU despite its name, channels 2-256-256-251-250-240-240-235-233-233-229-225-223-
  *                220-220-220-215-214-205-204-200
  * each with NN_11's paddings (circular pad of 1 before the unpadded first conv, zero padding 1 in the middle convs, the
  * last conv unpadded) and one linear layer from 200 * (d-2)^2 features to 3 outputs.  Same stacks in, same (P,3) f32
- * Q-table out as tq_nn11_forward.  Their learner step and optimizer stay with the caller.  Design: DESIGN.md 3.10.
+ * Q-table out as tq_nn11_forward.  Their learner step is tq_nnw_grad_* below; the optimizer stays with the caller.  Design:
+ * DESIGN.md 3.10.
  * Numerics contract -- NN_11's:
  *  - conv and linear weights are rounded once to bf16 (round to nearest even) when they are loaded; all biases stay f32.
  *  - a stack element is converted to bf16 (exact for the 0/1 the writer produces).
@@ -567,6 +568,42 @@ int tq_nnw_load(tq_nnw* h, const float* const* weights, const float* const* bias
 /* model(stack): stack[rows][2][d][d] of element type dtype (TQ_F32 / TQ_F16 / TQ_BF16 / TQ_U8, 16-byte aligned) -> q
  * f32[rows][3].  Any rows >= 0: the call walks passes of max_rows itself.  TQ_E_INVALID before the first tq_nnw_load. */
 int tq_nnw_forward(tq_nnw* h, const void* stack, int dtype, int64_t rows, float* q, void* stream);
+
+/* ---- The wide nets' learner step (src/Learner_mp.py:140-169): tq_nn11_grad_*'s for NN_8 and NN_17.  The optimizer works
+ * on the caller's f32 master parameters (torch.optim; there is no optimizer kernel for these nets), and tq_nnw_grad_load
+ * packs them again.  Design: DESIGN.md 3.12.
+ * Numerics contract: that of NN_11's learner step above, word for word, with these substitutions:
+ *   - the layers are l = 1..L, L = 8 (NN_8) or 20 (NN_17), over the channel lists of TQ_NET_NN8 / TQ_NET_NN17; A_L, G_L,
+ *     mask_L and conv L stand where A_11, G_11, mask_11 and conv11 do;
+ *   - the last conv is the unpadded one, so it is conv L's transpose that is the full correlation from the (d-2)^2 grid
+ *     onto the d^2 grid;
+ *   - the linear layer has 200 features per pixel (in a pitch of 224, the padding 0): dWlin is f32[3][200*(d-2)^2].
+ *  What carries over unchanged: q is f32 and bit-equal to tq_nnw_forward on the same weights and rows; the head is NN_11's
+ *  expression, each operation rounded once, left to right; G_l is stored as bf16 (RNE); the ReLU mask is A_l > 0 on the
+ *  stored bf16 activation; every product is bf16 x bf16 and every sum f32; the parameter gradients are f32 in torch
+ *  layout, written (not accumulated), gradients at the bf16-rounded weights; no gradient is formed for the stack; an
+ *  actions_idx outside 0..2 gives loss 0, dq 0 and latches TQ_E_ACTION.
+ *  Determinism: no atomics in any sum; how a sum is cut into partial sums depends on (net, layer, d, n) alone, never on
+ *  occupancy or timing: the same call gives the same bits.
+ * One handle, one stream, as for tq_nnw_*: create / destroy allocate and synchronise, load and step only enqueue. */
+typedef struct tq_nnw_grad tq_nnw_grad;
+/* net: TQ_NET_NN8 or TQ_NET_NN17.  Allocates both weight images, every layer's activation image (each of its layer's own
+ * padded channel count), two gradient images of max_batch * d*d * 256 bf16 and the wgrad partial images (one of 9 * 256 *
+ * 256 f32 per chunk of records; the chunk is a function of d alone) for steps of up to max_batch (1..4096) records.
+ * Checked before the device is touched: out NULL, net neither, d even or unsupported, max_batch outside 1..4096. */
+int tq_nnw_grad_create(tq_nnw_grad** out, int net, int d, int max_batch, int device);
+int tq_nnw_grad_destroy(tq_nnw_grad* h);
+/* weights / biases as for tq_nnw_load; packs the forward and the dgrad images on the device. */
+int tq_nnw_grad_load(tq_nnw_grad* h, const float* const* weights, const float* const* biases, void* stream);
+/* One step on state[n][2][d][d] (element type dtype, 16-byte aligned): actions_idx i64[n] in 0..2, y f32[n], w f32[n] or
+ * NULL -> q f32[n][3] (may be NULL), loss f32[n], and the gradients into grad_w[L + 1] / grad_b[L + 1], HOST arrays of
+ * device pointers to f32 tensors in the layout of tq_nnw_load's.  Checked before any launch (TQ_E_INVALID): n outside
+ * 1..max_batch, a NULL pointer, a misaligned state, a call before the first load.  The call allocates nothing and does not
+ * synchronise. */
+int tq_nnw_grad_step(tq_nnw_grad* h, const void* state, int dtype, int n, const int64_t* actions_idx, const float* y,
+                     const float* w, float* q, float* loss, float* const* grad_w, float* const* grad_b, void* stream);
+/* Reads and clears the handle's device error latch (synchronises `stream`): 0 or TQ_E_ACTION. */
+int tq_nnw_grad_check(tq_nnw_grad* h, void* stream);
 
 /* ---- The forward pass of the reference's BasicBlock ResNets on the device (src/nn/torch/ResNet.py), forward only and
  * with BatchNorm in inference form only (running statistics: the network as model.eval() computes it):

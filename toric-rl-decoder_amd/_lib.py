@@ -107,6 +107,11 @@ SYMBOLS = [
     ("tq_nnw_destroy", _i, [_vp]),
     ("tq_nnw_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
     ("tq_nnw_forward", _i, [_vp, _vp, _i, _i64, _vp, _vp]),
+    ("tq_nnw_grad_create", _i, [C.POINTER(_vp), _i, _i, _i, _i]),
+    ("tq_nnw_grad_destroy", _i, [_vp]),
+    ("tq_nnw_grad_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("tq_nnw_grad_step", _i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, C.POINTER(_vp), C.POINTER(_vp), _vp]),
+    ("tq_nnw_grad_check", _i, [_vp, _vp]),
     ("tq_resnet_create", _i, [C.POINTER(_vp), _i, _i, _i64, _i]),
     ("tq_resnet_destroy", _i, [_vp]),
     ("tq_resnet_load", _i, [_vp, C.POINTER(_vp), C.POINTER(_vp), _vp, _vp, _d, _vp]),

@@ -32,7 +32,7 @@ int nn11g_wgrad(const tq_nn11_grad* h, int l, const uint16_t* g, const void* sta
     const int cout = tq::nn11_cout(l), cpo = tq::nn11_cpad(cout);
     if (l == 1) {
         if (int rc = launch(tq::k_nn11_wgrad1, dim3(chunks), dim3(256), stream, g, stack, dtype, h->wpart, h->bpart, n, d)) return rc;
-        return launch_1d(tq::k_nn11_wreduce, (int64_t)cout * 18 + cout, stream, h->wpart, h->bpart, chunks, 1, cout, 18, cpo, 18, dw, db);
+        return launch_1d(tq::k_nn11_wreduce<tq::NN11_MAX_CP>, (int64_t)cout * 18 + cout, stream, h->wpart, h->bpart, chunks, 1, cout, 18, cpo, 18, dw, db);
     }
     const int cin = tq::nn11_cin(l), cpi = tq::nn11_cpad(cin);
     int rc;
@@ -42,7 +42,7 @@ int nn11g_wgrad(const tq_nn11_grad* h, int l, const uint16_t* g, const void* sta
                                     tq::nn11_mode(l), cpo / 32);
     else rc = fail(TQ_E_INVALID, "nn11 grad: no wgrad kernel for layer %d (%d padded input channels)", l, cpi);
     if (rc) return rc;
-    return launch_1d(tq::k_nn11_wreduce, (int64_t)9 * cout * cin + cout, stream, h->wpart, h->bpart, chunks, 9, cout, cin, cpo, cpi, dw, db);
+    return launch_1d(tq::k_nn11_wreduce<tq::NN11_MAX_CP>, (int64_t)9 * cout * cin + cout, stream, h->wpart, h->bpart, chunks, 9, cout, cin, cpo, cpi, dw, db);
 }
 
 template <int D>
@@ -54,10 +54,10 @@ int nn11g_step(const tq_nn11_grad* h, const void* state, int dtype, int n, const
     if (int rc = launch(tq::k_nn11_dblin, dim3(1), dim3(256), stream, h->dq, n, gb[L])) return rc;
     uint16_t* g = h->g[0];
     uint16_t* o = h->g[1];
-    if (int rc = launch_1d(tq::k_nn11_g11, (int64_t)n * F, stream, h->dq, h->net.limg, h->act[L], g, n, NPIX)) return rc;
+    if (int rc = launch_1d(tq::k_nn11_g11<64>, (int64_t)n * F, stream, h->dq, h->net.limg, h->act[L], g, n, NPIX)) return rc;
     const int slices = (n + tq::NN11_LIN_SLICE - 1) / tq::NN11_LIN_SLICE;
-    if (int rc = launch(tq::k_nn11_lin_part, dim3((F + 255) / 256, slices), dim3(256), stream, h->dq, h->act[L], h->lpart, n, NPIX)) return rc;
-    if (int rc = launch_1d(tq::k_nn11_lin_reduce, (int64_t)tq::NN11_OUT * F, stream, h->lpart, slices, NPIX, gw[L])) return rc;
+    if (int rc = launch(tq::k_nn11_lin_part<64>, dim3((F + 255) / 256, slices), dim3(256), stream, h->dq, h->act[L], h->lpart, n, NPIX)) return rc;
+    if (int rc = launch_1d(tq::k_nn11_lin_reduce<64, 64>, (int64_t)tq::NN11_OUT * F, stream, h->lpart, slices, NPIX, gw[L])) return rc;
     for (int l = L; l >= 1; --l) {
         if (int rc = nn11g_wgrad(h, l, g, state, dtype, n, gw[l - 1], gb[l - 1], stream)) return rc;
         if (l == 1) break;

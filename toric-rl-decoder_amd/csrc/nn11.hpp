@@ -266,6 +266,7 @@ struct NN11Shape {
 
 // The forward's epilogue, NN_11's and the wide nets': relu(sum + bias) over the layer's padded f32 bias.
 struct ConvBiasRelu {
+    using Aux = float;                                    // what a kernel's `aux` argument points to
     const float* bias;
     __device__ __forceinline__ float4 operator()(const float4& a, int c0, int64_t) const {
         const float4 b = *reinterpret_cast<const float4*>(bias + c0);
@@ -274,6 +275,7 @@ struct ConvBiasRelu {
 };
 // The dgrad's: the sum where the bf16 activation of `out`'s shape is > 0 (sign clear and not a zero), else 0.
 struct NN11DgradMask {
+    using Aux = uint16_t;
     const uint16_t* act;
     __device__ __forceinline__ float4 operator()(const float4& a, int, int64_t at) const {
         const uint2 m = *reinterpret_cast<const uint2*>(act + at);

@@ -77,10 +77,13 @@ __global__ __launch_bounds__(256) void k_nn11_dblin(const float* __restrict__ dq
     }
 }
 
-// G_11 = bf16(mask_11 * sum_a dq[.][a] Wlin_bf16[a][.]), one thread per element of conv11's image [n][npix][64]
+// The last conv layer's gradient and the linear layer's, over the feature pitch FEAT_CP of that layer's image: 64 for
+// NN_11 (l = 11), 224 with FEAT = 200 real channels for the wide nets (nnw_grad.hpp).
+// G_11 = bf16(mask_11 * sum_a dq[.][a] Wlin_bf16[a][.]), one thread per element of conv11's image [n][npix][FEAT_CP]
+template <int FEAT_CP>
 __global__ __launch_bounds__(256) void k_nn11_g11(const float* __restrict__ dq, const float* __restrict__ limg,
                                                   const uint16_t* __restrict__ a11, uint16_t* __restrict__ g11, int64_t n, int npix) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, F = (int64_t)npix * 64;
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, F = (int64_t)npix * FEAT_CP;
     if (e >= n * F) return;
     const int64_t i = e / F, f = e % F;
     float s = 0.f;
@@ -88,10 +91,11 @@ __global__ __launch_bounds__(256) void k_nn11_g11(const float* __restrict__ dq, 
     g11[e] = nn11_mask(a11[e]) ? nn11_bf16(s) : (uint16_t)0;
 }
 
-// dWlin partial sums: blockIdx.y = slice of NN11_LIN_SLICE records, one thread per feature f = pixel * 64 + channel
+// dWlin partial sums: blockIdx.y = slice of NN11_LIN_SLICE records, one thread per feature f = pixel * FEAT_CP + channel
+template <int FEAT_CP>
 __global__ __launch_bounds__(256) void k_nn11_lin_part(const float* __restrict__ dq, const uint16_t* __restrict__ a11,
                                                        float* __restrict__ lpart, int n, int npix) {
-    const int F = npix * 64, f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int F = npix * FEAT_CP, f = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (f >= F) return;
     const int i0 = (int)blockIdx.y * NN11_LIN_SLICE, i1 = i0 + NN11_LIN_SLICE < n ? i0 + NN11_LIN_SLICE : n;
     float s[NN11_OUT] = {0.f, 0.f, 0.f};
@@ -101,14 +105,18 @@ __global__ __launch_bounds__(256) void k_nn11_lin_part(const float* __restrict__
     }
     for (int o = 0; o < NN11_OUT; ++o) lpart[((int64_t)blockIdx.y * NN11_OUT + o) * F + f] = s[o];
 }
-// ... summed over the slices in index order, written in torch's (channel, y, x) feature order
+// ... summed over the slices in index order, written in torch's (channel, y, x) feature order over the FEAT real channels
+template <int FEAT_CP, int FEAT>
 __global__ __launch_bounds__(256) void k_nn11_lin_reduce(const float* __restrict__ lpart, int slices, int npix, float* __restrict__ dwlin) {
-    const int F = npix * 64, e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    const int F = npix * FEAT_CP, e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (e >= NN11_OUT * F) return;
     const int o = e / F, f = e % F;
+    constexpr bool POW2 = (FEAT_CP & (FEAT_CP - 1)) == 0;                   // NN_11's 64: a mask and a shift, as before
+    const int c = POW2 ? (f & (FEAT_CP - 1)) : f % FEAT_CP, pixel = POW2 ? (f >> __builtin_ctz(FEAT_CP)) : f / FEAT_CP;
+    if (FEAT < FEAT_CP && c >= FEAT) return;
     float s = 0.f;
     for (int k = 0; k < slices; ++k) s += lpart[((int64_t)k * NN11_OUT + o) * F + f];
-    dwlin[(int64_t)o * F + (int64_t)(f & 63) * npix + (f >> 6)] = s;
+    dwlin[(int64_t)o * (npix * FEAT) + (int64_t)c * npix + pixel] = s;
 }
 
 // conv1's wgrad (K operand 18 wide): plain f32 FMAs.  Workgroup = one chunk of records; thread = (output channel, input
@@ -232,7 +240,8 @@ __global__ __launch_bounds__(256) void k_nn11_wgrad(const uint16_t* __restrict__
 
 // dW (torch layout [cout][cin][taps], written) = the partial images summed in chunk order; db likewise.  wpart is
 // [chunk][taps][cpo][cpi] (conv1: taps = 1, its 18 k values as cin = cpi = 18); one thread per element, tap-major so
-// that neighbouring threads read neighbouring words.
+// that neighbouring threads read neighbouring words.  BPITCH: f32 per chunk in bpart (128; the wide nets: 256).
+template <int BPITCH>
 __global__ __launch_bounds__(256) void k_nn11_wreduce(const float* __restrict__ wpart, const float* __restrict__ bpart, int chunks, int taps,
                                                       int cout, int cin, int cpo, int cpi, float* __restrict__ dw, float* __restrict__ db) {
     const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x), nw = taps * cout * cin;
@@ -246,7 +255,7 @@ __global__ __launch_bounds__(256) void k_nn11_wreduce(const float* __restrict__ 
     } else if (e < nw + cout) {
         const int co = e - nw;
         float s = 0.f;
-        for (int c = 0; c < chunks; ++c) s += bpart[(int64_t)c * NN11_MAX_CP + co];
+        for (int c = 0; c < chunks; ++c) s += bpart[(int64_t)c * BPITCH + co];
         db[co] = s;
     }
 }

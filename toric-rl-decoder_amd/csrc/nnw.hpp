@@ -95,26 +95,29 @@ __global__ __launch_bounds__(256) void k_nnw_pack(NNWPack p, int s, int d, uint1
     }
 }
 
-// One conv3x3 + bias + ReLU layer of a wide net.  KS: k-steps of 16 input channels per tap (the stack layer: 2 steps over
-// its 18 k values), NT: tiles of 32 output channels, MODE: where a tap's source pixel lies.  `in`: the previous layer's
-// activation image [P][d^2][16 KS] (MODE != CIRCULAR) or the perspective stack [P][2][d][d] of element type `dtype`;
-// `out`: this layer's image [P][pixels][32 NT] ((d-2)^2 pixels for NN11_VALID); `bias`: its padded f32 bias.
+// One conv3x3 layer of a wide net.  KS: k-steps of 16 input channels per tap (the stack layer: 2 steps over its 18 k
+// values), NT: tiles of 32 output channels, MODE: where a tap's source pixel lies.  `in`: the previous layer's activation
+// image [P][d^2][16 KS] (MODE != CIRCULAR; (d-2)^2 pixels for NN11_FULL) or the perspective stack [P][2][d][d] of element
+// type `dtype`; `out`: this layer's image [P][pixels][32 NT] ((d-2)^2 pixels for NN11_VALID).
+// EPI says what becomes of the sums (nn11.hpp).  ConvBiasRelu, the forward: `aux` is the layer's padded f32 bias.
+// NN11DgradMask, the backward's dgrad over a dgrad image (nnw_grad.hpp): `aux` is the bf16 activation image of `out`'s
+// shape, whose sign masks.
 // Grid: (ceil(P / G), ceil(NT / CONV_NTB)) workgroups of NN11Geom<D>::THREADS threads: workgroup (x, y) computes the
 // n-tiles 4 y .. of the perspectives G x ..
-template <int D, int KS, int NT, int MODE>
+template <int D, int KS, int NT, int MODE, class EPI = ConvBiasRelu>
 __global__ __launch_bounds__(NN11Geom<D>::THREADS) void k_nnw_conv(const void* __restrict__ in, int dtype, const uint16_t* __restrict__ wimg,
-                                                  const float* __restrict__ bias, uint16_t* __restrict__ out, int64_t P) {
+                                                  const typename EPI::Aux* __restrict__ aux, uint16_t* __restrict__ out, int64_t P) {
     using Shape = NN11Shape<D, MODE>;
     __shared__ __attribute__((aligned(16))) unsigned char lds[conv_lds_bytes<Shape, KS>()];
     constexpr int REM = NT % CONV_NTB;                                      // n-tiles of the last block row, if fewer
     const int n0 = (int)blockIdx.y * CONV_NTB;
     if constexpr (REM != 0) {
         if (n0 + CONV_NTB > NT) {                                           // uniform over the workgroup
-            conv_tiles<Shape, KS, NT, REM>(lds, n0, in, dtype, wimg, out, P, ConvBiasRelu{bias});
+            conv_tiles<Shape, KS, NT, REM>(lds, n0, in, dtype, wimg, out, P, EPI{aux});
             return;
         }
     }
-    conv_tiles<Shape, KS, NT, CONV_NTB>(lds, n0, in, dtype, wimg, out, P, ConvBiasRelu{bias});
+    conv_tiles<Shape, KS, NT, CONV_NTB>(lds, n0, in, dtype, wimg, out, P, EPI{aux});
 }
 #endif  // __HIPCC__
 

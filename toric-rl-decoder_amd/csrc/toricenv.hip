@@ -769,4 +769,5 @@ int tq_check(tq_env* h, void* stream_) {
 #include "abi_nn11_grad.hpp"
 #include "abi_nn11_opt.hpp"
 #include "abi_nnw.hpp"
+#include "abi_nnw_grad.hpp"
 #include "abi_resnet.hpp"

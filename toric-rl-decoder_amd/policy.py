@@ -4,7 +4,7 @@ The Q-network NN_11 (nn11.py: the torch module, same parameter names as the refe
 unchanged, and its HIP counterparts NN11Forward / NN11Grad / NN11Optimizer) is imported here, so that BASELINE
 configs[2] ("generatePerspective feeding NN_11 policy for selectAction") and the evaluation loop can run without the
 reference's Python.  An NN11Forward is accepted wherever a ``model`` is, and so is an NNWideForward (nnw.py: the
-reference's NN_8 and NN_17, forward only) and a ResNetForward (resnet.py: the launcher's default ResNet18, and ResNet34,
+reference's NN_8 and NN_17, whose learner step is NNWideGrad) and a ResNetForward (resnet.py: the launcher's default ResNet18, and ResNet34,
 eval-mode forward only).
 
   selectActionBatch    src/numba/util_actor.py:11-53
@@ -20,13 +20,14 @@ from . import _lib
 from ._lib import _ptr, _stream, check, to_device
 from .envset import EnvSet, ToricEnv, generatePerspectiveBatch
 from .nn11 import NN_11, NN11Forward, NN11Grad, NN11Optimizer  # noqa: F401  (their callers import them from here)
-from .nnw import NN_8, NN_17, NNWideForward  # noqa: F401  (the wide nets, forward only: nnw.py)
+from .nnw import NN_8, NN_17, NNWideForward, NNWideGrad  # noqa: F401  (the wide nets, forward and learner step: nnw.py)
 from .resnet import ResNet18, ResNet34, ResNetForward  # noqa: F401  (the BasicBlock ResNets, eval-mode forward only: resnet.py)
 
 
 def learnerStep(grad, target_model, memory, optimizer, batch_size, beta, discount=0.95, batch=None):
     """One iteration of Learner_mp.py:135-169 on a device PrioritizedReplayMemory: sample_batch -> learnerTargets on
-    ``target_model`` (a torch module or an NN11Forward) -> ``grad.backward`` -> ``optimizer.step()`` on the masters ->
+    ``target_model`` (a torch module or a forward handle) -> ``grad.backward`` (``grad``: an NN11Grad or an NNWideGrad) ->
+    ``optimizer.step()`` on the masters ->
     ``grad.load()`` (not after an optimizer that ``repacks``: NN11Optimizer) -> priority_update(indices, |loss|).  ``batch``: a sample_batch result to step on instead of drawing
     one (its next_state is not used).  -> (loss f32 (B,), indices i64 (B,)) device tensors."""
     if batch is None:
