@@ -216,7 +216,11 @@ int tq_states_persp_write(int d, int n, const uint8_t* states, const int64_t* of
  * offsets i64[N+1], positions i32[P,3], eps f64[N] -> actions i32[N,4], q_values f32[N,3].
  * greedy iff (1-eps) > U; greedy = first maximum in row-major order; otherwise a uniform
  * perspective and op (Philox, keyed by the lattice's episode and step counters).
- * q_table may be NULL when every eps is 1 (pure exploration: the Q-values are never read). */
+ * q_table may be NULL when every eps is 1 (pure exploration: the Q-values are never read).
+ * Non-finite values -- selection (tq_select_action, tq_select_action_planned, tq_states_select_action alike).  The greedy
+ * choice is np.argmax of the slice in row-major order: the first NaN if the slice holds one, else the first maximum (+inf
+ * included; the first element of a slice of -inf).  q_values is the chosen row as it stands, NaN and inf included.  The
+ * planned selection stays bit-identical to the dense one.  The index always lies inside the slice. */
 int tq_select_action(tq_env* h, const float* q_table, const int64_t* offsets,
                      const int32_t* positions, const double* eps, int32_t* actions,
                      float* q_values, void* stream);
@@ -274,7 +278,13 @@ int tq_segment_max(const float* q_table, const int64_t* offsets, int n, const in
  * `largest` argument, no host read).  q_table f32[P,3] (may be NULL when P = 0), offsets i64[n+1], rewards f32[n],
  * terminals u8[n] (0/1, a torch.bool tensor) -> y f32[n].  f32 arithmetic with the roundings of the torch expression
  * reward + (~terminal).float() * discount * target -- ((1 - t) * discount) * m, then + reward, then the clamp, nothing
- * contracted -- so y is bit-identical to that expression on the same inputs. */
+ * contracted -- so y is bit-identical to that expression on the same inputs.
+ * Non-finite values -- targets (tq_segment_max, tq_td_target, and max_a of tq_block_priorities alike).  A maximum is
+ * np.amax: NaN if any element of the slice is NaN, else the largest, +-inf included.  The zero padding of a shorter slice
+ * keeps a NaN a NaN (and turns -inf into 0, as max(-inf, 0) is).  The target expression is plain IEEE: 0 x NaN and 0 x inf
+ * under a set terminal flag are NaN, as in torch, and the clamp passes NaN.  So a NaN Q-value of the target network gives a
+ * NaN y (and a NaN priority) and never a finite number.  Out of scope: a NaN priority saved into the replay memory's sum
+ * tree (tq_replay_save_block, tq_replay_update) -- the reference's tree breaks there as well. */
 int tq_td_target(const float* q_table, const int64_t* offsets, int n, const float* rewards,
                  const uint8_t* terminals, float discount, float lo, float hi, float* y, void* stream);
 
@@ -426,7 +436,17 @@ int tq_replay_check(tq_replay* r, void* stream);
  *    bf16 (RNE) as the next layer's input; conv11's output is rounded the same way.
  *  - the linear layer accumulates in f32, adds the f32 bias and stores f32: Q-values are never rounded to 16 bits.
  *  - no atomics: the same call on the same inputs gives bit-identical output.
- *  - channels are padded with zero weights and biases up to the MFMA granule (32), so a padded activation channel is 0.
+ *  - channels are padded with zero weights and biases up to the MFMA granule (32), so a padded activation channel is 0
+ *    (on finite data: see "Non-finite values").
+ * Non-finite values -- forward (NN_11, the wide nets and the ResNets alike).  A NaN in any input of a sum gives a NaN in
+ * every output that depends on it, as the torch expression of the same operation does; NaNs are compared by position
+ * only, their payload and sign are unspecified.  relu(NaN) = NaN, relu(+-0) = +0, relu(+inf) = +inf, relu(-inf) = +0.
+ * bf16(x) is RNE for every finite x, +-inf for |x| at or beyond the rounding boundary (0x7f7f8000), and a NaN for every
+ * NaN -- also for those whose low half would carry out of the exponent (0x7fffffff, 0xffffffff, 0x7f800001).  The zero
+ * padding of a conv and the zero weights of a padded channel multiply like any other 0: 0 x inf and 0 x NaN are NaN, as in
+ * torch, so an inf weight makes its output channel NaN where the activation it meets is 0, the padding included.  Rows
+ * never meet: a non-finite stack element changes no other row's Q-values, and what a call leaves in the handle's scratch
+ * changes no later call.  Finite inputs give the bits they gave before these rules were written down.
  * One handle, one stream: the calls of a handle share its packed weights and activation scratch; issue them on one
  * stream, or separate them by a synchronisation.  create / destroy are set-up calls (allocate, synchronise, leave the
  * caller's device unchanged); load and forward only enqueue kernels. */
@@ -465,7 +485,8 @@ int tq_nn11_check(tq_nn11* h, void* stream);
  *     mean_i(loss[i]) (Learner_mp.py:152-160);  w == NULL means all ones;
  *   - actions_idx[i] outside 0..2: loss[i] = 0, dq[i] = 0, and TQ_E_ACTION is latched (tq_nn11_grad_check).
  *  Gradients of the pre-activations, G_l for layer l, stored as bf16 (RNE; bf16 has f32's exponent range: no loss scaling):
- *   - the ReLU mask is A_l > 0 on the stored bf16 activation;
+ *   - the ReLU mask is A_l > 0 on the stored bf16 activation, and a NaN activation lets the gradient through: the mask
+ *     blocks where A_l <= 0 (torch's threshold_backward);
  *   - G_11 = bf16(mask_11 * sum_a dq[.][a] * Wlin_bf16[a][.]);
  *   - l = 11..2: G_{l-1} = bf16(mask_{l-1} * conv_transpose(G_l, W_l rounded to bf16)), accumulated in f32; conv11 is
  *     unpadded, so its transpose is a full correlation from the (d-2)^2 grid onto the d^2 grid;
@@ -477,6 +498,11 @@ int tq_nn11_check(tq_nn11* h, void* stream);
  *   - these are gradients at the bf16-rounded weights, to be applied to the f32 masters (straight-through).
  *  Determinism: no atomics in any sum; how a sum is cut into partial sums depends on (d, n) alone, never on occupancy or
  *  timing: the same call gives the same bits.  A padded channel's G is 0 because its mask is 0.
+ *  Non-finite values -- learner step.  The forward's rules hold for A_l and q.  The head is plain IEEE: a NaN y, an inf w
+ *  or a NaN q[i][a] gives record i a non-finite loss[i] and dq[i][a] and leaves loss and q of every other record unchanged
+ *  in bits.  Every sum of the backward (G_l, dW_l, db_l, dWlin, dblin) propagates like the forward's, the bf16 of a G as
+ *  above: a gradient element is NaN where the f32 autograd of this contract makes it one.  A step full of NaN leaves
+ *  nothing in the handle's scratch that a later step reads.
  * One handle, one stream, as for tq_nn11_*: create / destroy allocate and synchronise, load and step only enqueue. */
 typedef struct tq_nn11_grad tq_nn11_grad;
 /* Allocates both weight images, the eleven activation images (each of its layer's own padded channel count), two gradient
@@ -500,7 +526,8 @@ int tq_nn11_grad_check(tq_nn11_grad* h, void* stream);
  * Design: DESIGN.md 3.8.
  * Numerics contract.  Per element, all in f32, each operation rounded once in the order the parentheses give, nothing
  * contracted; sqrt and / are IEEE correctly rounded (hipcc's default for f32, which the contract relies on) and subnormals
- * are kept.  NaN and Inf propagate as IEEE has it; nothing is clamped.
+ * are kept.  NaN and Inf propagate as IEEE has it; nothing is clamped: a NaN or inf gradient element makes p' a NaN, and
+ * the element's place in every image one (bf16 as in the forward's contract: a NaN stays a NaN).
  *  Scalars: computed on the host in double as Python does (b^t is pow), each cast to f32 once; t = step, the 1-based count
  *  of this update.
  *  TQ_OPT_ADAM:  c1 = (float)(1 - beta1), c2 = (float)beta2, c3 = (float)(1 - beta2), cb = (float)sqrt(1 - beta2^t),

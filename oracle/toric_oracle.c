@@ -280,9 +280,11 @@ void tor_select_action(int n, const float *q_table, const int64_t *offsets, cons
         draw(seed, (uint32_t)(first_env + e), episodes[e], steps[e], TOR_DOMAIN_SEL, 0, w);
         int64_t p; int op;
         if ((1.0 - eps[e]) > u01(w[0])) {
-            int64_t best = 0; float bv = q_table[3 * lo];
-            for (int64_t k = 1; k < 3 * (hi - lo); ++k)
-                if (q_table[3 * lo + k] > bv) { bv = q_table[3 * lo + k]; best = k; }
+            int64_t best = 0; float bv = q_table[3 * lo];         /* np.argmax: the first NaN, else the first maximum */
+            for (int64_t k = 1; k < 3 * (hi - lo) && bv == bv; ++k) {
+                const float x = q_table[3 * lo + k];
+                if (x > bv || x != x) { bv = x; best = k; }
+            }
             p = best / 3; op = (int)(best % 3);
         } else {
             p = mulhi(w[1], (uint32_t)(hi - lo)); op = (int)mulhi(w[2], 3);

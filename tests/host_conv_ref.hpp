@@ -41,23 +41,33 @@ inline void conv_host(const float* W, int taps, int ksteps, int ntiles, int osid
                       Src src, Epi epi, uint16_t* out) {
     const int cpi = ksteps * 16, cpo = ntiles * 32, opix = oside * oside;
     float acc[MAX_CP];
+    // rows of W that hold an inf or a NaN: 0 times such a weight is a NaN, so the term is not left out, not even for
+    // the zero padding (torch and the MFMA kernels multiply there as well)
+    const int wrows = (stack ? 1 : taps) * cpi;
+    std::vector<uint8_t> odd(wrows, 0);
+    bool any_odd = false;
+    for (int r = 0; r < wrows; ++r) {
+        for (int c = 0; c < cpo && !odd[r]; ++c) odd[r] = !(W[(size_t)r * cpo + c] - W[(size_t)r * cpo + c] == 0.f);
+        any_odd = any_odd || odd[r];
+    }
     for (int o = 0; o < opix; ++o) {
         for (int c = 0; c < cpo; ++c) acc[c] = 0.f;
         for (int tap = 0; tap < taps; ++tap) {
             const int sp = src(o / oside, o % oside, tap);
-            if (sp < 0) continue;                                       // the zero padding
+            if (sp < 0 && !any_odd) continue;                           // the zero padding
             if (stack) {
                 for (int ci = 0; ci < 2; ++ci) {
-                    const float a = nn11_f32(nn11_bf16((float)stack[ci * in_pix + sp]));
-                    if (a == 0.f) continue;
-                    const float* w = W + (size_t)nn11_k1(ci, tap) * cpo;
+                    const int k = nn11_k1(ci, tap);
+                    const float a = sp < 0 ? 0.f : nn11_f32(nn11_bf16((float)stack[ci * in_pix + sp]));
+                    if (a == 0.f && !odd[k]) continue;
+                    const float* w = W + (size_t)k * cpo;
                     for (int c = 0; c < cpo; ++c) acc[c] += a * w[c];
                 }
                 continue;
             }
             for (int k = 0; k < cpi; ++k) {
-                const float a = nn11_f32(in[nn11_act_index(0, sp, k, in_pix, cpi)]);
-                if (a == 0.f) continue;                                 // adds +0: the sum is the same without it
+                const float a = sp < 0 ? 0.f : nn11_f32(in[nn11_act_index(0, sp, k, in_pix, cpi)]);
+                if (a == 0.f && !odd[tap * cpi + k]) continue;          // adds +0: the sum is the same without it
                 const float* w = W + ((size_t)tap * cpi + k) * cpo;
                 for (int c = 0; c < cpo; ++c) acc[c] += a * w[c];
             }
@@ -112,7 +122,7 @@ inline void forward_one(int d, const PackedNet& net, const uint8_t* stack, uint1
         conv_host<MAX_CP>(net.wt[l].data(), 9, conv_ksteps(y.cin), conv_ntiles(y.cout), y.mode == NN11_VALID ? d - 2 : d, d * d,
                   l == 1 ? stack : nullptr, act[l - 1],
                   [&](int oy, int ox, int tap) { return nn11_src_pixel(y.mode, d, oy, ox, tap); },
-                  [&](float sum, int c, int64_t) { const float v = sum + bias[c]; return v > 0.f ? v : 0.f; }, act[l]);
+                  [&](float sum, int c, int64_t) { return nn11_relu(sum + bias[c]); }, act[l]);
     }
     const int npix = nn11_out_pixels(d), fcp = nn11_cpad(net.layer[L - 1].cout);
     for (int a = 0; a < NN11_OUT; ++a) {

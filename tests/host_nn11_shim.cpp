@@ -22,3 +22,12 @@ extern "C" int shim_nn11_forward(int d, const float* const* weights, const float
 
 // perspectives per workgroup of the conv kernels (the tile edge tests/test_gpu_nn11.py aims at)
 extern "C" int shim_nn11_group(int d) { return nn11_group(d); }
+
+// nn11_bf16 itself, element by element: what packs weights and stores stacks, activations and gradients
+extern "C" void shim_nn11_bf16(const float* x, int64_t n, uint16_t* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = nn11_bf16(x[i]);
+}
+// ... and the backward's ReLU mask over stored bf16 activations
+extern "C" void shim_nn11_mask(const uint16_t* a, int64_t n, uint8_t* out) {
+    for (int64_t i = 0; i < n; ++i) out[i] = nn11_mask(a[i]) ? 1 : 0;
+}

@@ -74,7 +74,7 @@ extern "C" int shim_resnet_forward(int net, int d, const float* const* conv_weig
                       [&](float sum, int ch, int64_t at) {
                           float v = sum * pk[i].scale[ch] + pk[i].shift[ch];
                           if (epi == RESNET_EPI_ADD_RELU) v = v + nn11_f32(res[at]);
-                          if (epi != RESNET_EPI_NONE) v = v > 0.f ? v : 0.f;
+                          if (epi != RESNET_EPI_NONE) v = nn11_relu(v);
                           return v;
                       }, out);
         };

@@ -17,7 +17,7 @@ extern "C" void shim_td_target(const float* q, const int64_t* offsets, int n, co
     for (int e = 0; e < n; ++e) {
         const int64_t first = offsets[e], cnt = offsets[e + 1] - first;
         float best = -INFINITY;
-        for (int64_t k = 0; k < 3 * cnt; ++k) best = fmaxf(best, q[3 * first + k]);
+        for (int64_t k = 0; k < 3 * cnt; ++k) best = tq::td_max(best, q[3 * first + k]);
         y[e] = tq::td_target_value(rewards[e], terminals[e], discount, tq::td_next_max(best, cnt, longest), lo, hi);
     }
 }

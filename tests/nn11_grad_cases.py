@@ -91,29 +91,54 @@ class RoundBoth(torch.autograd.Function):
         return g.bfloat16().float(), None, None
 
 
-def _rounded_weights(sd, dtype):
+def _rounded_weights(sd, dtype, exact=True):
     if dtype == torch.float64:
-        return {k: (K.round_bf16(v.double()) if k.endswith("weight") else v.double()) for k, v in sd.items()}
+        return {k: (K.round_bf16(v.double(), "rne", exact) if k.endswith("weight") else v.double()) for k, v in sd.items()}
     return {k: (v.float().bfloat16().float() if k.endswith("weight") else v.float()) for k, v in sd.items()}
 
 
-def reference_backward(sd, x, dq, dtype=torch.float64):
+def reference_backward(sd, x, dq, dtype=torch.float64, exact=None, pad_explicitly=False):
     """The contract by autograd: weights rounded to bf16, the activation rounded after each ReLU, the gradient rounded
     where it passes that point on the way back (so G_l = bf16(mask_l * ...), the mask applied by ReLU's own backward to
     the rounded gradient: a rounded value keeps its sign and a zero stays zero, so mask and rounding commute).
     ``x`` (n, 2, d, d), ``dq`` (n, 3) the gradient of the loss with respect to q, or a function of q (detached) that
     gives it -> (q, {parameter name: gradient}).  dtype float32: the same in f32 torch ops, the yardstick for trained
-    weights."""
-    exact = dtype == torch.float64
-    p = {k: v.clone().requires_grad_(True) for k, v in _rounded_weights(sd, dtype).items()}
+    weights.  ``exact`` (default: float64 only): assert that f32 holds every rounded value.
+    pad_explicitly: the zero padding of conv2..10 as F.pad before an unpadded conv2d, so that its zeros are terms of
+    every sum like any other (0 x NaN = NaN), which is the contract.  torch's padded conv2d has no single answer there:
+    its f32 CPU kernels leave the padding's terms out, its f64 ones multiply them -- the NaN tests use this switch."""
+    L = len(sd) // 2 - 1                                                  # any plain net: nnw_grad_cases binds this one
+    exact = dtype == torch.float64 if exact is None else exact
+    p = {k: v.clone().requires_grad_(True) for k, v in _rounded_weights(sd, dtype, exact).items()}
     a = x.to(dtype)
-    a = F.pad(K.round_bf16(a) if exact else a.bfloat16().float(), (1, 1, 1, 1), mode="circular")
-    for l in range(1, 12):
-        pre = F.conv2d(a, p[f"conv{l}.weight"], p[f"conv{l}.bias"], padding=0 if l in (1, 11) else 1)
+    a = F.pad(K.round_bf16(a, "rne", exact) if dtype == torch.float64 else a.bfloat16().float(), (1, 1, 1, 1), mode="circular")
+    for l in range(1, L + 1):
+        pad = 0 if l in (1, L) else 1
+        if pad and pad_explicitly:
+            a, pad = F.pad(a, (1, 1, 1, 1)), 0
+        pre = F.conv2d(a, p[f"conv{l}.weight"], p[f"conv{l}.bias"], padding=pad)
         a = RoundBoth.apply(F.relu(pre), "rne", exact)
     q = F.linear(a.flatten(1), p["linear1.weight"], p["linear1.bias"])
     q.backward((dq(q.detach()) if callable(dq) else dq).to(dtype))
     return q.detach(), {k: v.grad for k, v in p.items()}
+
+
+# ---- NaN and inf in one record of a step (tests/test_gpu_nonfinite.py; the comparisons are plain_cases') ------------------
+LEARNER_POISONS = ("y nan", "weight inf", "stack nan")
+
+
+def poisoned_batch(kind, r, x, y, w):
+    """copies of the f32 tensors (x (n, 2, d, d), y (n,), w (n,)) with record ``r`` poisoned: its target a NaN, its
+    importance weight +inf, or one element of its stack a NaN"""
+    assert kind in LEARNER_POISONS, kind
+    x, y, w = x.clone(), y.clone(), w.clone()
+    if kind == "y nan":
+        y[r] = float("nan")
+    elif kind == "weight inf":
+        w[r] = float("inf")
+    else:
+        x[r, 1, x.shape[-1] // 2, 0] = float("nan")
+    return x, y, w
 
 
 def _wgrad(inp, shape, g, padding):

@@ -20,7 +20,8 @@ import torch
 import torch.nn.functional as F
 
 import nnw_cases as K
-from nn11_grad_cases import MUTANT_LAYER, MUTANTS, SUM_LIMIT, RoundBoth, head_contract, play_memory, tie_records  # noqa: F401
+from nn11_grad_cases import (LEARNER_POISONS, MUTANT_LAYER, MUTANTS, SUM_LIMIT, RoundBoth, head_contract, play_memory,  # noqa: F401
+                             _rounded_weights, poisoned_batch, reference_backward, tie_records)
 
 NETS = K.NETS
 
@@ -59,30 +60,6 @@ def wgrad_persp(d):
 def row_counts(d):
     """one record; one more than a conv workgroup's perspectives; one more than a wgrad chunk's records (a two-chunk sum)"""
     return sorted({1, K.group(d) + 1, wgrad_persp(d) + 1})
-
-
-def _rounded_weights(sd, dtype):
-    if dtype == torch.float64:
-        return {k: (K.round_bf16(v.double()) if k.endswith("weight") else v.double()) for k, v in sd.items()}
-    return {k: (v.float().bfloat16().float() if k.endswith("weight") else v.float()) for k, v in sd.items()}
-
-
-def reference_backward(sd, x, dq, dtype=torch.float64):
-    """nn11_grad_cases.reference_backward with L = the state_dict's conv layers: weights rounded to bf16, the activation
-    rounded after each ReLU, the gradient rounded where it passes that point on the way back.  ``x`` (n, 2, d, d), ``dq``
-    (n, 3) the gradient of the loss with respect to q, or a function of q (detached) that gives it -> (q, {parameter
-    name: gradient}).  dtype float32: the same in f32 torch ops, the yardstick for dense weights."""
-    L = len(sd) // 2 - 1
-    exact = dtype == torch.float64
-    p = {k: v.clone().requires_grad_(True) for k, v in _rounded_weights(sd, dtype).items()}
-    a = x.to(dtype)
-    a = F.pad(K.round_bf16(a) if exact else a.bfloat16().float(), (1, 1, 1, 1), mode="circular")
-    for l in range(1, L + 1):
-        pre = F.conv2d(a, p[f"conv{l}.weight"], p[f"conv{l}.bias"], padding=0 if l in (1, L) else 1)
-        a = RoundBoth.apply(F.relu(pre), "rne", exact)
-    q = F.linear(a.flatten(1), p["linear1.weight"], p["linear1.bias"])
-    q.backward((dq(q.detach()) if callable(dq) else dq).to(dtype))
-    return q.detach(), {k: v.grad for k, v in p.items()}
 
 
 def _wgrad(inp, shape, g, padding):

@@ -128,19 +128,21 @@ def layer_outputs(model, x):
         return outs, model.linear1(x.flatten(1))
 
 
-def _r(t):
-    return t.bfloat16().float()
+def _r(t, dtype=torch.float32):
+    """rounded to bf16, held as ``dtype``"""
+    return t.float().bfloat16().to(dtype)
 
 
-def contract_forward(model, x):
+def contract_forward(model, x, dtype=torch.float32):
     """The contract in torch ops: weights .bfloat16().float(), f32 conv2d, .bfloat16().float() after each ReLU, an f32
-    linear on rounded weights; biases f32."""
+    linear on rounded weights; biases f32.  ``dtype``: float64 runs the same roundings with float64 sums (what
+    order_free_pattern compares with)."""
     with torch.no_grad():
-        x = F.pad(_r(x.float()), (1, 1, 1, 1), mode="circular")
+        x = F.pad(_r(x, dtype), (1, 1, 1, 1), mode="circular")
         for i in range(model.layers):
             c = getattr(model, f"conv{i + 1}")
-            x = _r(F.relu(F.conv2d(x, _r(c.weight), c.bias, padding=c.padding)))
-        return F.linear(x.flatten(1), _r(model.linear1.weight), model.linear1.bias)
+            x = _r(F.relu(F.conv2d(x, _r(c.weight, dtype), c.bias.to(dtype), padding=c.padding)), dtype)
+        return F.linear(x.flatten(1), _r(model.linear1.weight, dtype), model.linear1.bias.to(dtype))
 
 
 def rms(a, b):
@@ -358,3 +360,68 @@ def dense_rows_for(d):
     """the row count of the dense case at size d: 2 G + 3 perspectives cross the tile, workgroup and pass edges of a
     handle of G + 1 rows"""
     return 2 * group(d) + 3
+
+
+# ---- NaN and inf ----------------------------------------------------------------------------------------------------
+# The contract (include/toricenv.h): NaN and inf go where the torch / numpy expression of the operation sends them.  A
+# NaN is compared by position only; an inf by position and sign; everything else bit for bit.  Non-finite values enter a
+# case only as literal NaN / inf elements or as one f32 weight beyond bf16's range, never as finite values near
+# overflow, so where they end up does not depend on the order of a sum -- which order_free_pattern asserts case by case.
+FINITE, NAN, PLUS_INF, MINUS_INF = 0, 1, 2, 3
+OVER_BF16 = 3.4e38                             # an f32 that RNE takes to bf16's +inf (the boundary is 0x7f7f8000 = 3.396e38)
+WEIGHT_POISONS = ("nan weight", "inf weight", "nan bias")
+
+
+def as_numpy(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def pattern(a):
+    """-> int8 array: FINITE, NAN, PLUS_INF or MINUS_INF per element"""
+    a = as_numpy(a)
+    return (np.isnan(a) * NAN + np.isposinf(a) * PLUS_INF + np.isneginf(a) * MINUS_INF).astype(np.int8)
+
+
+def same_pattern(got, want):
+    got, want = as_numpy(got), as_numpy(want)
+    return got.shape == want.shape and np.array_equal(pattern(got), pattern(want))
+
+
+def same_bits_nan_equal(got, want):
+    """NaNs at the same places (np.isnan equality; payload and sign free), every other element the same bits"""
+    got, want = as_numpy(got), as_numpy(want)
+    if got.shape != want.shape or got.dtype != want.dtype or not np.array_equal(np.isnan(got), np.isnan(want)):
+        return False
+    keep = ~np.isnan(got)
+    u = {2: np.uint16, 4: np.uint32, 8: np.uint64}[got.dtype.itemsize]
+    return np.array_equal(np.ascontiguousarray(got).view(u)[keep], np.ascontiguousarray(want).view(u)[keep])
+
+
+def order_free_pattern(forward, *args):
+    """forward(*args, dtype=...) in f32 and in f64 -> the f32 result, after asserting that both have the same NaN / inf
+    pattern and that it holds a non-finite value at all: a case that fails this is not one."""
+    q32, q64 = forward(*args, dtype=torch.float32), forward(*args, dtype=torch.float64)
+    assert same_pattern(q32, q64), "where NaN / inf end up depends on the precision of the sums: not a case"
+    assert pattern(q32).any(), "the poison does not reach the output: not a case"
+    return q32
+
+
+def poisoned_state_dict(sd, weight, bias, kind, at=0, bias_at=0):
+    """A copy of ``sd`` with one element replaced (WEIGHT_POISONS): element ``at`` of the flattened tensor ``weight`` by
+    NaN or by OVER_BF16, or element ``bias_at`` of ``bias`` by NaN."""
+    assert kind in WEIGHT_POISONS, kind
+    out = {k: v.clone() for k, v in sd.items()}
+    key, value = (bias, float("nan")) if kind == "nan bias" else (weight, float("nan") if kind == "nan weight" else OVER_BF16)
+    out[key].view(-1)[bias_at if kind == "nan bias" else at] = value
+    if kind == "inf weight":
+        assert bool(torch.isfinite(out[key]).all()) and bool(torch.isinf(out[key].bfloat16()).any())
+    return out
+
+
+def poison_rows(d, rows):
+    """the rows of a call of ``rows`` perspectives on a handle of G + 1 that get a poisoned stack element: the first, the
+    last of a workgroup and the first of the second pass"""
+    g = group(d)
+    at = sorted({0, g - 1, g + 1})
+    assert at[-1] < rows
+    return at

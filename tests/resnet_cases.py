@@ -179,30 +179,35 @@ def fold(sd, bn, eps=EPS):
     return s, sd[bn + ".bias"].float() - sd[bn + ".running_mean"].float() * s
 
 
-def _r(t):
-    return t.bfloat16().float()
+def _r(t, dtype=torch.float32):
+    """rounded to bf16, held as ``dtype``"""
+    return t.float().bfloat16().to(dtype)
 
 
-def contract_forward(model, x, eps=EPS):
+def contract_forward(model, x, eps=EPS, dtype=torch.float32):
     """The contract in torch ops, f32: weights and the stack .bfloat16().float(), f32 conv2d, acc s + t with the folded
     f32 vectors, the residual added before the ReLU, .bfloat16().float() after each ReLU and on the shortcut convolution's
-    image, the pool as an f32 sum, the linear layer on rounded weights, divided by s^2, + bias."""
+    image, the pool as an f32 sum, the linear layer on rounded weights, divided by s^2, + bias.  ``dtype``: float64 runs
+    the same roundings and the same f32 fold with float64 sums (what plain_cases.order_free_pattern compares with)."""
     sd = model.state_dict()
     stem, blocks = graph(net_of(sd))
 
+    def r(t):
+        return _r(t, dtype)
+
     def cv(a, conv, bn, stride=1):
-        w = _r(sd[conv + ".weight"].float())
-        s, t = fold(sd, bn, eps)
+        w = r(sd[conv + ".weight"])
+        s, t = (v.to(dtype) for v in fold(sd, bn, eps))
         return F.conv2d(a, w, stride=stride, padding=w.shape[-1] // 2) * s[None, :, None, None] + t[None, :, None, None]
 
     with torch.no_grad():
-        a = _r(F.relu(cv(_r(x.float()), *stem)))
+        a = r(F.relu(cv(r(x), *stem)))
         for c1, c2, sc, stride in blocks:
-            mid = _r(F.relu(cv(a, *c1, stride)))
-            r = _r(cv(a, *sc, stride)) if sc else a
-            a = _r(F.relu(cv(mid, *c2) + r))
+            mid = r(F.relu(cv(a, *c1, stride)))
+            res = r(cv(a, *sc, stride)) if sc else a
+            a = r(F.relu(cv(mid, *c2) + res))
         pooled = a.sum((2, 3))
-        return pooled @ _r(sd["linear.weight"].float()).T / float(a.shape[2] * a.shape[3]) + sd["linear.bias"].float()
+        return pooled @ r(sd["linear.weight"]).T / float(a.shape[2] * a.shape[3]) + sd["linear.bias"].to(dtype)
 
 
 # ---- the float64 reference.  Every term of every sum is a multiple of one power of two and the sum of the terms'

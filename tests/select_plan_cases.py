@@ -86,3 +86,34 @@ def oracle_reads(q_table, offsets, positions, eps, seed, env_ids, episodes, step
         if hi > lo:
             reads += list(range(lo, hi)) if greedy[i] else [int(chosen[i])]
     return act, qv, np.array(reads, np.int64)
+
+
+# ---- slices with NaN and inf (tests/test_nonfinite_host.py, tests/test_gpu_nonfinite.py) ---------------------------------
+SLICE_LENGTHS = (1, 21, 22, 43)                # 3 cnt = 3, 63, 66, 129: below, at and beyond one and two rounds of 64 lanes
+
+
+def nonfinite_slices():
+    """-> (q (P,3) f32, offsets): for every length the finite slice, a NaN at each of the flat positions 0, 63, 64 and the
+    last that the slice has, NaNs at two of them (the first wins), all NaN, all -inf, and NaN with +inf on either side."""
+    rng = np.random.default_rng(404)
+    slices = []
+    for cnt in SLICE_LENGTHS:
+        base = rng.normal(size=3 * cnt).astype(np.float32)
+        base[rng.integers(0, 3 * cnt, 2)] = base.max()                          # a tie of maxima: the first one counts
+        at = sorted({p for p in (0, 63, 64, 3 * cnt - 1) if p < 3 * cnt})
+        slices.append(base.copy())
+        for p in at:
+            s = base.copy()
+            s[p] = np.float32(np.nan)
+            slices.append(s)
+        s = base.copy()
+        s[[at[-1], at[len(at) // 2]]] = np.float32(np.nan)
+        slices.append(s)
+        slices.append(np.full(3 * cnt, np.float32(np.nan)))
+        slices.append(np.full(3 * cnt, -np.float32(np.inf)))
+        for nan_at, inf_at in ((at[-1], 0), (0, at[-1])) if cnt > 1 else ((2, 0), (0, 2)):
+            s = base.copy()
+            s[nan_at], s[inf_at] = np.float32(np.nan), np.float32(np.inf)
+            slices.append(s)
+    off = np.concatenate([[0], np.cumsum([s.size // 3 for s in slices])]).astype(np.int64)
+    return np.concatenate(slices).reshape(-1, 3), off

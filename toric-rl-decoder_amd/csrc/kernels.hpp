@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256) void k_block_priorities(BlockView b, int64_t n
         double qn = 0.0, qv = 0.0;
         if (q) {
             const float* nx = q + 3 * (s + n);                // row (t+1, e)
-            qn = (double)fmaxf(fmaxf(nx[0], nx[1]), nx[2]);
+            qn = (double)td_max(td_max(nx[0], nx[1]), nx[2]);   // np.amax: a NaN stays
             qv = (double)q[3 * s + (op - 1)];
         }
         const double m = discount * qn;
@@ -509,13 +509,13 @@ __global__ __launch_bounds__(256) void k_select(const float* __restrict__ q, con
         int bk = 0x7fffffff;
         for (int k = lane; k < 3 * n; k += 64) {
             const float x = q[3 * lo + k];
-            if (x > best) { best = x; bk = k; }               // strict >: first maximum within the lane
+            if (sel_beats(x, k, best, bk)) { best = x; bk = k; }   // first NaN, else first maximum within the lane
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ob = __shfl_xor(best, o, 64);
             const int ok = __shfl_xor(bk, o, 64);
-            if (ob > best || (ob == best && ok < bk)) { best = ob; bk = ok; }
+            if (sel_beats(ob, ok, best, bk)) { best = ob; bk = ok; }
         }
         bk = bk == 0x7fffffff ? 0 : bk;
         pidx = bk / 3; a = bk - 3 * pidx;
@@ -542,11 +542,11 @@ __global__ __launch_bounds__(256) void k_segment_max(const float* __restrict__ q
     const int64_t lo = offsets[e];
     const int cnt = (int)(offsets[e + 1] - lo);
     float best = -__builtin_inff();
-    for (int k = lane; k < 3 * cnt; k += 64) best = fmaxf(best, q[3 * lo + k]);
+    for (int k = lane; k < 3 * cnt; k += 64) best = td_max(best, q[3 * lo + k]);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+    for (int o = 32; o > 0; o >>= 1) best = td_max(best, __shfl_xor(best, o, 64));
     if (cnt == 0) best = 0.f;
-    else if (largest && cnt < *largest) best = fmaxf(best, 0.f);
+    else if (largest && cnt < *largest) best = td_max(best, 0.f);
     if (lane == 0) out[e] = best;
 }
 
@@ -579,9 +579,9 @@ __global__ __launch_bounds__(256) void k_td_target(const float* __restrict__ q, 
         const int64_t first = offsets[e];
         const int64_t cnt = offsets[e + 1] - first;
         float best = -__builtin_inff();
-        for (int64_t k = lane; k < 3 * cnt; k += 64) best = fmaxf(best, q[3 * first + k]);
+        for (int64_t k = lane; k < 3 * cnt; k += 64) best = td_max(best, q[3 * first + k]);
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1) best = fmaxf(best, __shfl_xor(best, o, 64));
+        for (int o = 32; o > 0; o >>= 1) best = td_max(best, __shfl_xor(best, o, 64));
         if (lane == 0) y[e] = td_target_value(rewards[e], terminals[e], discount, td_next_max(best, cnt, longest), lo, hi);
     }
 }

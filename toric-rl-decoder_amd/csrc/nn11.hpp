@@ -71,7 +71,8 @@ TQ_HD int nn11_bias_offset(int l) {                // first f32 of layer l in th
 TQ_HD int nn11_out_pixels(int d) { return (d - 2) * (d - 2); }
 TQ_HD int64_t nn11_lin_elems(int d) { return (int64_t)NN11_OUT * nn11_out_pixels(d) * 64; }
 
-// ---- bf16, round to nearest even (finite inputs; NaN is not produced by this network's arithmetic on finite weights)
+// ---- bf16, round to nearest even; beyond the rounding boundary +-inf; a NaN stays a NaN (its quiet bit is set, so
+// that the rounding's carry cannot turn it into +-0 or inf)
 TQ_HD uint16_t nn11_bf16(float f) {
     uint32_t u;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -79,8 +80,9 @@ TQ_HD uint16_t nn11_bf16(float f) {
 #else
     memcpy(&u, &f, 4);
 #endif
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
+    // one select, no early return: a branch here is not if-converted, and the conv epilogue calls this per output
+    const uint32_t rne = u + (0x7fffu + ((u >> 16) & 1u)), nan = u | 0x00400000u;
+    return (uint16_t)((f != f ? nan : rne) >> 16);
 }
 TQ_HD float nn11_f32(uint16_t b) {
     const uint32_t u = (uint32_t)b << 16;
@@ -93,8 +95,12 @@ TQ_HD float nn11_f32(uint16_t b) {
 #endif
 }
 
-// the ReLU mask of the backward pass: a stored bf16 activation is > 0 (activations are never negative or NaN)
-TQ_HD bool nn11_mask(uint16_t a) { return a != 0 && !(a & 0x8000u); }
+// relu as torch has it: +0 for x <= 0, x otherwise, so that a NaN stays (fmaxf would drop it)
+TQ_HD float nn11_relu(float x) { return x <= 0.f ? 0.f : x; }
+
+// the ReLU mask of the backward pass, torch's threshold_backward: the gradient passes unless the stored bf16
+// activation is <= 0.  The forward stores +0, a positive value or a NaN (either sign), and a NaN lets it through.
+TQ_HD bool nn11_mask(uint16_t a) { return (a & 0x7fffu) > 0x7f80u || (a != 0 && !(a & 0x8000u)); }
 
 // ---- weight image of one layer: element <-> (cout, k, tap)
 TQ_HD int64_t nn11_wimg_index(int tap, int kstep, int ntile, int lane, int j, int ksteps, int ntiles) {
@@ -270,10 +276,10 @@ struct ConvBiasRelu {
     const float* bias;
     __device__ __forceinline__ float4 operator()(const float4& a, int c0, int64_t) const {
         const float4 b = *reinterpret_cast<const float4*>(bias + c0);
-        return make_float4(fmaxf(a.x + b.x, 0.f), fmaxf(a.y + b.y, 0.f), fmaxf(a.z + b.z, 0.f), fmaxf(a.w + b.w, 0.f));
+        return make_float4(nn11_relu(a.x + b.x), nn11_relu(a.y + b.y), nn11_relu(a.z + b.z), nn11_relu(a.w + b.w));
     }
 };
-// The dgrad's: the sum where the bf16 activation of `out`'s shape is > 0 (sign clear and not a zero), else 0.
+// The dgrad's: the sum where nn11_mask passes the bf16 activation of `out`'s shape (> 0 or a NaN), else 0.
 struct NN11DgradMask {
     using Aux = uint16_t;
     const uint16_t* act;

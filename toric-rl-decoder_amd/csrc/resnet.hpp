@@ -176,7 +176,7 @@ struct ResNetScaleShift {
             v.x += nn11_f32((uint16_t)rr.x); v.y += nn11_f32((uint16_t)(rr.x >> 16));
             v.z += nn11_f32((uint16_t)rr.y); v.w += nn11_f32((uint16_t)(rr.y >> 16));
         }
-        if (epi != RESNET_EPI_NONE) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+        if (epi != RESNET_EPI_NONE) { v.x = nn11_relu(v.x); v.y = nn11_relu(v.y); v.z = nn11_relu(v.z); v.w = nn11_relu(v.w); }
         return v;
     }
 };

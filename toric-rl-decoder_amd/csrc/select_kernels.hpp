@@ -86,13 +86,13 @@ __global__ __launch_bounds__(256) void k_select_planned(const float* __restrict_
         int bk = 0x7fffffff;
         for (int k = lane; k < 3 * n; k += 64) {
             const float x = q_rows[3 * plo + k];
-            if (x > best) { best = x; bk = k; }               // strict >: first maximum within the lane
+            if (sel_beats(x, k, best, bk)) { best = x; bk = k; }   // first NaN, else first maximum within the lane
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float ob = __shfl_xor(best, o, 64);
             const int ok2 = __shfl_xor(bk, o, 64);
-            if (ob > best || (ob == best && ok2 < bk)) { best = ob; bk = ok2; }
+            if (sel_beats(ob, ok2, best, bk)) { best = ob; bk = ok2; }
         }
         bk = bk == 0x7fffffff ? 0 : bk;
         pidx = bk / 3; a = bk - 3 * pidx; qrow = pidx;

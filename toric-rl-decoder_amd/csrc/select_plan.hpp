@@ -29,13 +29,22 @@ TQ_HD int sel_random_op(const U4& w) { return (int)mulhi32(w.z, 3); }
 // ... and the one row it reads: lo = offsets[e]
 TQ_HD int64_t sel_random_row(const U4& w, int64_t lo, int n) { return lo + sel_random_persp(w, n); }
 
-// First maximum of a lattice's slice in row-major order (:93-95) as the flat index 3 * perspective + op; 0 for a slice
-// without a value above -inf.  What the wave-wide search of k_select / k_select_planned computes; here for the host.
+// np.argmax's order on (value, flat index) pairs: does (x, k) come before (best, bk)?  A NaN comes before every number,
+// the larger of two numbers before the smaller, and the lower index first among NaNs or equal numbers.
+TQ_HD bool sel_beats(float x, int k, float best, int bk) {
+    const bool xn = x != x, bn = best != best;
+    if (xn || bn) return xn && (!bn || k < bk);
+    return x > best || (x == best && k < bk);
+}
+
+// np.argmax of a lattice's slice in row-major order (:93-95) as the flat index 3 * perspective + op: the first NaN if
+// there is one, else the first maximum (0 for a slice of -inf).  What the wave-wide search of k_select /
+// k_select_planned computes; here for the host.
 inline int sel_first_max(const float* q, int n) {
     float best = -__builtin_inff();
     int bk = 0;
     for (int k = 0; k < 3 * n; ++k)
-        if (q[k] > best) { best = q[k]; bk = k; }
+        if (sel_beats(q[k], k, best, bk)) { best = q[k]; bk = k; }
     return bk;
 }
 

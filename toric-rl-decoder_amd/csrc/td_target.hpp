@@ -13,12 +13,15 @@
 
 namespace tq {
 
+// np.amax's step: a NaN on either side gives a NaN, two numbers give fmaxf's answer bit for bit.
+TQ_HD float td_max(float a, float b) { return a != a ? a : (b != b ? b : fmaxf(a, b)); }
+
 // max_q: the maximum over the slice (anything for an empty one); largest: the longest slice of the batch.  The
 // reference pads every slice with zero rows up to the longest before the argmax (:98-100), so a shorter slice gets
-// max(max_q, 0); a state without perspectives (terminal) gives 0 (:74-76,108).
+// max(max_q, 0), which keeps a NaN maximum a NaN; a state without perspectives (terminal) gives 0 (:74-76,108).
 TQ_HD float td_next_max(float max_q, int64_t cnt, int64_t largest) {
     if (cnt == 0) return 0.f;
-    return (cnt < largest && !(max_q > 0.f)) ? 0.f : max_q;
+    return (cnt < largest && max_q <= 0.f) ? 0.f : max_q;
 }
 
 TQ_HD float td_target_value(float reward, int terminal, float discount, float m, float lo, float hi) {
