@@ -1,86 +1,32 @@
 // The wide nets' learner step: the tq_nnw_grad_* entry points of include/toricenv.h (part of toricenv.hip's translation
-// unit), abi_nn11_grad.hpp restated over slot s of the network table.
-// Device memory of a handle for steps of up to B = max_batch records of net s at size d, beside the packed network and
-// its dgrad images (L = nnw_layers(s), cp = channels rounded up to 32, p = nnw_wgrad_persp(d), bf16 = 2 bytes):
-//   activations   sum over l = 1..L of B * pixels(l) * cp(cout(l)) bf16      (pixels: (d-2)^2 for l = L, else d^2)
-//   gradients     2 * B * d^2 * 256 bf16
-//   partials      ceil(B / p) * (9 * 256 * 256 + 256) f32  +  ceil(B / 64) * 3 * 224 (d-2)^2 f32
-//   q, dq         2 * B * 3 f32
+// unit): slot s of the network table described to the shell all learner-step handles share (abi_grad.hpp, which lists a
+// handle's device memory).
 #pragma once
-#include "abi_nn11_grad.hpp"
+#include "abi_grad.hpp"
 #include "abi_nnw.hpp"
 
-struct tq_nnw_grad {                       // made by `new tq_nnw_grad()`: every member starts as zero
-    int d, device, max_batch;
-    NNWNet net;                            // as tq_nnw's, with the dgrad images
-    uint16_t* act[tq::NNW_MAX_LAYERS + 1]; // act[l], l = 1..L: layer l's bf16 output, max_batch * pixels(l) * cpad(cout(l))
-    uint16_t* g[2];                        // gradient images taking turns: max_batch * d^2 * 256 bf16 each
-    float* q;                              // f32[max_batch][3], used when the caller passes no q
-    float* dq;                             // f32[max_batch][3]
-    float* wpart;                          // wgrad partial images, one of NNW_WPART_ELEMS f32 per chunk of records
-    float* bpart;                          // bias partials f32[chunks][256]
-    float* lpart;                          // linear partials f32[slices][3][224 (d-2)^2]
-    int* latch;
-    DeviceBuffers mem;
-};
+struct tq_nnw_grad : GradHandle<NNWNet, tq::NNW_MAX_LAYERS> {};
 
 namespace {
-// G_l (in `g`) -> the gradient of layer l - 1's pre-activation (in `out`), l = 2..L: the convolution over layer l's dgrad
-// image, masked by the sign of act[l - 1]
-template <int D>
-int nnwg_dgrad(const tq_nnw_grad* h, int l, const uint16_t* g, uint16_t* out, int64_t n, hipStream_t stream) {
-    const int s = h->net.slot;
-    return nnw_conv<D, tq::NN11DgradMask>(l == tq::nnw_layers(s) ? tq::NN11_FULL : tq::NN11_ZERO, tq::conv_dksteps(tq::nnw_cout(s, l)),
-                                          tq::conv_dntiles(tq::nnw_cin(s, l)), g, 0, h->net.dimg + tq::nnw_dimg_offset(s, l),
-                                          h->act[l - 1], out, n, stream);
-}
-
-// dW_l and db_l from G_l (in `g`) and layer l's input, l = 1..L
-int nnwg_wgrad(const tq_nnw_grad* h, int l, const uint16_t* g, const void* stack, int dtype, int64_t n, float* dw, float* db,
-               hipStream_t stream) {
-    constexpr int W = tq::NNW_WG_WAVES;
-    const int s = h->net.slot, d = h->d, chunks = (int)tq::nnw_wgrad_chunks(d, n);
-    const int cout = tq::nnw_cout(s, l), cpo = tq::nn11_cpad(cout);
-    if (l == 1) {
-        if (cpo != tq::NNW_MAX_CP) return fail(TQ_E_INVALID, "nnw grad: no conv1 wgrad kernel for %d padded output channels", cpo);
-        if (int rc = launch(tq::k_nnw_wgrad1, dim3(chunks), dim3(512), stream, g, stack, dtype, h->wpart, h->bpart, n, d)) return rc;
-        return launch_1d(tq::k_nn11_wreduce<tq::NNW_MAX_CP>, (int64_t)cout * 18 + cout, stream, h->wpart, h->bpart, chunks, 1, cout, 18, cpo,
-                         18, dw, db);
+struct NNWGradNet {
+    static constexpr const char* NAME = "nnw";
+    static constexpr int WAVES = tq::NNW_WG_WAVES, CHUNK_ROWS = tq::NNW_WG_CHUNK_ROWS, FEAT_CP = tq::NNW_FEAT_CP, FEAT = tq::NNW_FEAT;
+    int s;                                 // tq::nnw_slot(net)
+    int layers() const { return tq::nnw_layers(s); }
+    int cin(int l) const { return tq::nnw_cin(s, l); }
+    int cout(int l) const { return tq::nnw_cout(s, l); }
+    int mode(int l) const { return tq::nnw_mode(s, l); }
+    int64_t dimg_offset(int l) const { return tq::nnw_dimg_offset(s, l); }
+    template <int D>
+    int forward(const NNWNet& net, const void* state, int dtype, int64_t n, uint16_t* const* act, float* q, hipStream_t stream) const {
+        return nnw_forward<D>(net, state, dtype, n, act, q, stream);
     }
-    const int cin = tq::nnw_cin(s, l), cpi = tq::nn11_cpad(cin), mt = cpo / 32;
-    const dim3 grid(chunks, 9, (mt + W - 1) / W), block(W * 64);
-    int rc;
-    if (mt > 8) rc = fail(TQ_E_INVALID, "nnw grad: no wgrad kernel for layer %d (%d padded output channels)", l, cpo);
-    else if (cpi == 256) rc = launch(tq::k_nnw_wgrad<8, W>, grid, block, stream, g, h->act[l - 1], h->wpart, h->bpart, n, d, tq::nnw_mode(s, l), mt);
-    else if (cpi == 224) rc = launch(tq::k_nnw_wgrad<7, W>, grid, block, stream, g, h->act[l - 1], h->wpart, h->bpart, n, d, tq::nnw_mode(s, l), mt);
-    else rc = fail(TQ_E_INVALID, "nnw grad: no wgrad kernel for layer %d (%d padded input channels)", l, cpi);
-    if (rc) return rc;
-    return launch_1d(tq::k_nn11_wreduce<tq::NNW_MAX_CP>, (int64_t)9 * cout * cin + cout, stream, h->wpart, h->bpart, chunks, 9, cout, cin, cpo,
-                     cpi, dw, db);
-}
-
-template <int D>
-int nnwg_step(const tq_nnw_grad* h, const void* state, int dtype, int n, const int64_t* actions, const float* y, const float* w,
-              float* q, float* loss, float* const* gw, float* const* gb, hipStream_t stream) {
-    constexpr int NPIX = tq::NN11Geom<D>::OPIX, CP = tq::NNW_FEAT_CP, F = NPIX * CP;
-    const int L = tq::nnw_layers(h->net.slot);
-    if (int rc = nnw_forward<D>(h->net, state, dtype, n, h->act, q, stream)) return rc;       // every layer's output kept
-    if (int rc = launch_1d(tq::k_nn11_head, n, stream, q, actions, y, w, n, loss, h->dq, h->latch)) return rc;
-    if (int rc = launch(tq::k_nn11_dblin, dim3(1), dim3(256), stream, h->dq, n, gb[L])) return rc;
-    uint16_t* g = h->g[0];
-    uint16_t* o = h->g[1];
-    if (int rc = launch_1d(tq::k_nn11_g11<CP>, (int64_t)n * F, stream, h->dq, h->net.limg, h->act[L], g, n, NPIX)) return rc;
-    const int slices = (n + tq::NN11_LIN_SLICE - 1) / tq::NN11_LIN_SLICE;
-    if (int rc = launch(tq::k_nn11_lin_part<CP>, dim3((F + 255) / 256, slices), dim3(256), stream, h->dq, h->act[L], h->lpart, n, NPIX)) return rc;
-    if (int rc = launch_1d(tq::k_nn11_lin_reduce<CP, tq::NNW_FEAT>, (int64_t)tq::NN11_OUT * F, stream, h->lpart, slices, NPIX, gw[L])) return rc;
-    for (int l = L; l >= 1; --l) {
-        if (int rc = nnwg_wgrad(h, l, g, state, dtype, n, gw[l - 1], gb[l - 1], stream)) return rc;
-        if (l == 1) break;
-        if (int rc = nnwg_dgrad<D>(h, l, g, o, n, stream)) return rc;
-        uint16_t* t = g; g = o; o = t;
+    template <int D>
+    int dgrad(int mode, int ks, int nt, const uint16_t* g, const uint16_t* img, const uint16_t* mask, uint16_t* out, int64_t n,
+              hipStream_t stream) const {
+        return nnw_conv<D, tq::NN11DgradMask>(mode, ks, nt, g, 0, img, mask, out, n, stream);
     }
-    return TQ_OK;
-}
+};
 }  // namespace
 
 extern "C" {
@@ -88,25 +34,9 @@ extern "C" {
 int tq_nnw_grad_destroy(tq_nnw_grad* h) { return destroy_handle(h); }
 
 int tq_nnw_grad_create(tq_nnw_grad** out, int net, int d, int max_batch, int device) {
-    auto batch_check = [&] {
-        return max_batch < 1 || max_batch > 4096 ? fail(TQ_E_INVALID, "max_batch must be in 1..4096 (got %d)", max_batch) : (int)TQ_OK;
-    };
-    return create_handle(out, "nnw grad", d, device, [&] { return nnw_net_check(net); }, batch_check, [&](tq_nnw_grad* h) {
-        h->max_batch = max_batch;
-        const int s = tq::nnw_slot(net), L = tq::nnw_layers(s);
-        const size_t n = (size_t)max_batch;
-        h->net.alloc(h->mem, s, d, true);
-        for (int l = 1; l <= L; ++l)
-            h->mem.zeroed(&h->act[l], n * tq::nnw_layer_pixels(s, l, d) * tq::nn11_cpad(tq::nnw_cout(s, l)) * sizeof(uint16_t));
-        for (int i = 0; i < 2; ++i) h->mem.zeroed(&h->g[i], n * d * d * tq::NNW_MAX_CP * sizeof(uint16_t));
-        h->mem.zeroed(&h->q, n * tq::NN11_OUT * sizeof(float));
-        h->mem.zeroed(&h->dq, n * tq::NN11_OUT * sizeof(float));
-        const size_t chunks = (size_t)tq::nnw_wgrad_chunks(d, max_batch);
-        h->mem.zeroed(&h->wpart, chunks * tq::NNW_WPART_ELEMS * sizeof(float));
-        h->mem.zeroed(&h->bpart, chunks * tq::NNW_MAX_CP * sizeof(float));
-        const size_t slices = (n + tq::NN11_LIN_SLICE - 1) / tq::NN11_LIN_SLICE;
-        h->mem.zeroed(&h->lpart, slices * (size_t)tq::nnw_lin_elems(d) * sizeof(float));
-        h->mem.zeroed(&h->latch, 16);
+    return grad_create(out, "nnw grad", d, max_batch, device, [&] { return nnw_net_check(net); }, [&](tq_nnw_grad* h) {
+        h->net.alloc(h->mem, tq::nnw_slot(net), d, true);
+        return NNWGradNet{h->net.slot};
     });
 }
 
@@ -118,25 +48,12 @@ int tq_nnw_grad_load(tq_nnw_grad* h, const float* const* weights, const float* c
 int tq_nnw_grad_step(tq_nnw_grad* h, const void* state, int dtype, int n, const int64_t* actions_idx, const float* y, const float* w,
                      float* q, float* loss, float* const* grad_w, float* const* grad_b, void* stream_) {
     ENTER(h, "nnw grad handle");
-    if (!h->net.loaded) return fail(TQ_E_INVALID, "nnw grad step before tq_nnw_grad_load");
-    if (dtype < TQ_F32 || dtype > TQ_U8) return fail(TQ_E_INVALID, "bad state dtype %d", dtype);
-    if (n <= 0 || n > h->max_batch) return fail(TQ_E_INVALID, "n must be in 1..max_batch = %d (got %d)", h->max_batch, n);
-    if (!state || !actions_idx || !y || !loss) return fail(TQ_E_INVALID, "state / actions_idx / y / loss is NULL");
-    if (!grad_w || !grad_b) return fail(TQ_E_INVALID, "grad_w / grad_b is NULL");
-    for (int i = 0; i <= tq::nnw_layers(h->net.slot); ++i)
-        if (!grad_w[i] || !grad_b[i]) return fail(TQ_E_INVALID, "grad_w[%d] / grad_b[%d] is NULL", i, i);
-    REQUIRE_ALIGNED16(state, "state");
-    return by_size(h->d, [&](auto D) {
-        return nnwg_step<D()>(h, state, dtype, n, actions_idx, y, w, q ? q : h->q, loss, grad_w, grad_b, stream);
-    });
+    return grad_step(NNWGradNet{h->net.slot}, h, state, dtype, n, actions_idx, y, w, q, loss, grad_w, grad_b, stream);
 }
 
 int tq_nnw_grad_check(tq_nnw_grad* h, void* stream_) {
     ENTER(h, "nnw grad handle");
-    int flag = 0;
-    if (int rc = read_latch(h->latch, stream, &flag)) return rc;
-    if (flag & tq::NN11_ERR_ACTION) return fail(TQ_E_ACTION, "nnw grad step: an actions_idx outside 0..2 was given");
-    return TQ_OK;
+    return grad_check(NNWGradNet{h->net.slot}, h, stream);
 }
 
 }  // extern "C"

@@ -141,22 +141,31 @@ inline void conv_pack_layer_host(int cin, int cout, int taps, const float* w, co
     for (int c = 0; c < cp; ++c) bias[c] = c < cout ? b[c] : 0.f;
 }
 
-// ---- dgrad weight image of layer l = 2..11: the image of the convolution that takes G_l (cout(l) channels) to the
-// gradient of layer l - 1's output (cin(l) channels).  Same fragment order with the two channel counts in each other's
-// place and the taps flipped: element (cout' = ci, k = co, tap') = W_l[co][ci][8 - tap'].
-TQ_HD int nn11_dksteps(int l) { return nn11_cpad(nn11_cout(l)) / 16; }
-TQ_HD int nn11_dntiles(int l) { return nn11_cpad(nn11_cin(l)) / 32; }
-TQ_HD int64_t nn11_dimg_elems(int l) { return (int64_t)9 * nn11_dksteps(l) * nn11_dntiles(l) * 512; }
+// ---- dgrad weight image of one 3x3 layer by its channel counts: the image of the convolution that takes G_l (cout
+// channels) to the gradient of the layer's input (cin channels).  The forward's fragment order with the two channel counts
+// in each other's place and the taps flipped: element (cout' = ci, k = co, tap') = W[co][ci][8 - tap'].
+TQ_HD int conv_dksteps(int cout) { return nn11_cpad(cout) / 16; }
+TQ_HD int conv_dntiles(int cin) { return nn11_cpad(cin) / 32; }
+TQ_HD int64_t conv_dimg_elems(int cin, int cout) { return (int64_t)9 * conv_dksteps(cout) * conv_dntiles(cin) * 512; }
+TQ_HD float conv_dimg_value(int cin, int cout, int64_t idx, const float* w) {
+    const NN11WCoord c = nn11_wimg_coord(idx, conv_dksteps(cout), conv_dntiles(cin));      // .cout: ci, .k: co
+    if (c.cout >= cin || c.k >= cout) return 0.f;
+    return w[((int64_t)c.k * cin + c.cout) * 9 + (8 - c.tap)];
+}
+inline void conv_pack_dgrad_host(int cin, int cout, const float* w, uint16_t* dimg) {
+    const int64_t n = conv_dimg_elems(cin, cout);
+    for (int64_t i = 0; i < n; ++i) dimg[i] = nn11_bf16(conv_dimg_value(cin, cout, i, w));
+}
+// layer l = 2..11
+TQ_HD int nn11_dksteps(int l) { return conv_dksteps(nn11_cout(l)); }
+TQ_HD int nn11_dntiles(int l) { return conv_dntiles(nn11_cin(l)); }
+TQ_HD int64_t nn11_dimg_elems(int l) { return conv_dimg_elems(nn11_cin(l), nn11_cout(l)); }
 TQ_HD int64_t nn11_dimg_offset(int l) {            // first element of layer l = 2..12 in the handle's one dgrad image
     int64_t o = 0;
     for (int i = 2; i < l; ++i) o += nn11_dimg_elems(i);
     return o;
 }
-TQ_HD float nn11_dimg_value(int l, int64_t idx, const float* w) {
-    const NN11WCoord c = nn11_wimg_coord(idx, nn11_dksteps(l), nn11_dntiles(l));       // .cout: ci, .k: co
-    if (c.cout >= nn11_cin(l) || c.k >= nn11_cout(l)) return 0.f;
-    return w[((int64_t)c.k * nn11_cin(l) + c.cout) * 9 + (8 - c.tap)];
-}
+TQ_HD float nn11_dimg_value(int l, int64_t idx, const float* w) { return conv_dimg_value(nn11_cin(l), nn11_cout(l), idx, w); }
 
 // ---- linear image [a][pixel][64] <- torch [a][c * npix + pixel]
 TQ_HD int64_t nn11_lin_index(int a, int pixel, int c, int npix) { return ((int64_t)a * npix + pixel) * 64 + c; }
@@ -209,8 +218,7 @@ inline void nn11_pack_layer_host(int l, const float* w, const float* b, uint16_t
     conv_pack_layer_host(nn11_cin(l), nn11_cout(l), 9, w, b, wimg, bias);
 }
 inline void nn11_pack_dgrad_host(int l, const float* w, uint16_t* dimg) {       // l = 2..11
-    const int64_t n = nn11_dimg_elems(l);
-    for (int64_t i = 0; i < n; ++i) dimg[i] = nn11_bf16(nn11_dimg_value(l, i, w));
+    conv_pack_dgrad_host(nn11_cin(l), nn11_cout(l), w, dimg);
 }
 inline void nn11_pack_linear_host(int d, const float* w, float* limg) {
     const int64_t n = nn11_lin_elems(d);

@@ -8,6 +8,9 @@
 // a time through LDS TRANSPOSED ([channel][row], the A operand already shifted by the tap) and reads 16-byte fragments
 // from there.  A workgroup takes nn11_wgrad_persp(d) records and one tap and writes an f32 partial image; k_nn11_wreduce
 // sums the partial images in index order and writes torch's layout.  How a sum is cut depends on (d, n) alone.
+//
+// The wgrad kernels (k_conv_wgrad, k_conv_wgrad1) and the dgrad pack's body (conv_pack_dgrad) are written by channel
+// counts, wave count and rows per chunk: the wide nets' learner step (nnw_grad.hpp) runs the same ones.
 #pragma once
 #include "nn11.hpp"
 
@@ -18,8 +21,11 @@ constexpr int NN11_WG_PITCH = NN11_WG_ROWS * 2 + 16;      // bytes of one channe
 constexpr int NN11_LIN_SLICE = 64;                        // records per partial sum of the linear layer's weight gradient
 constexpr int NN11_ERR_ACTION = 1;                        // the latch: an actions_idx outside 0..2 was seen
 
-// records per wgrad workgroup: about 1024 rows
-TQ_HD int nn11_wgrad_persp(int d) { const int p = 1024 / (d * d); return p < 2 ? 2 : p; }
+// records per wgrad workgroup (a chunk): about chunk_rows rows of the GEMM, 1024 for NN_11
+TQ_HD int conv_wgrad_persp(int chunk_rows, int d) { const int p = chunk_rows / (d * d); return p < 2 ? 2 : p; }
+constexpr int NN11_WG_WAVES = 4;                          // wavefronts of a wgrad workgroup: one per tile of 32 output channels
+constexpr int NN11_WG_CHUNK_ROWS = 1024;
+TQ_HD int nn11_wgrad_persp(int d) { return conv_wgrad_persp(NN11_WG_CHUNK_ROWS, d); }
 TQ_HD int64_t nn11_wgrad_chunks(int d, int64_t n) { const int p = nn11_wgrad_persp(d); return (n + p - 1) / p; }
 constexpr int64_t NN11_WPART_ELEMS = (int64_t)9 * NN11_MAX_CP * NN11_MAX_CP;      // f32 per partial image, at most
 // layer l's output grid: (d-2)^2 pixels for conv11, d^2 otherwise
@@ -36,12 +42,15 @@ TQ_HD NN11Head nn11_head(float q, float y, float w, int n) {
 }
 
 #if defined(__HIPCC__)
+// the dgrad image `img` of one layer from its torch weight `w`: what one block row of a pack kernel does
+__device__ __forceinline__ void conv_pack_dgrad(int cin, int cout, const float* w, uint16_t* img) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = conv_dimg_elems(cin, cout);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride) img[e] = nn11_bf16(conv_dimg_value(cin, cout, e, w));
+}
+// one block row (blockIdx.y) per layer l = y + 2
 __global__ __launch_bounds__(256) void k_nn11_pack_dgrad(NN11Pack p, uint16_t* dimg) {
     const int l = (int)blockIdx.y + 2;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x, n = nn11_dimg_elems(l);
-    uint16_t* img = dimg + nn11_dimg_offset(l);
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += stride)
-        img[e] = nn11_bf16(nn11_dimg_value(l, e, p.w[l - 1]));
+    conv_pack_dgrad(nn11_cin(l), nn11_cout(l), p.w[l - 1], dimg + nn11_dimg_offset(l));
 }
 
 // one thread per record
@@ -119,13 +128,16 @@ __global__ __launch_bounds__(256) void k_nn11_lin_reduce(const float* __restrict
     dwlin[(int64_t)o * (npix * FEAT) + (int64_t)c * npix + pixel] = s;
 }
 
-// conv1's wgrad (K operand 18 wide): plain f32 FMAs.  Workgroup = one chunk of records; thread = (output channel, input
-// channel) with its nine taps; the stack is read with the circular wrap.  Partial image [chunk][128][18], and the
-// chunk's bias partial [chunk][128].
-__global__ __launch_bounds__(256) void k_nn11_wgrad1(const uint16_t* __restrict__ g, const void* __restrict__ stack, int dtype,
-                                                     float* __restrict__ wpart, float* __restrict__ bpart, int64_t P, int d) {
-    const int pix = d * d, pw = nn11_wgrad_persp(d);
-    const int co = threadIdx.x & 127, ci = threadIdx.x >> 7;
+// conv1's wgrad (K operand 18 wide): plain f32 FMAs.  CP: the padded output channels, 128 for NN_11 and 256 for the wide
+// nets.  Workgroup = one chunk of records, 2 CP threads; thread = (output channel, input channel) with its nine taps; the
+// stack is read with the circular wrap.  g: G_1 [P][d^2][CP].  Partial image [chunk][CP][18], and the chunk's bias partial
+// [chunk][CP].
+template <int CP, int CHUNK_ROWS>
+__global__ __launch_bounds__(2 * CP) void k_conv_wgrad1(const uint16_t* __restrict__ g, const void* __restrict__ stack, int dtype,
+                                                        float* __restrict__ wpart, float* __restrict__ bpart, int64_t P, int d) {
+    static_assert((CP & (CP - 1)) == 0, "a thread's channels are a mask and a shift of its index");
+    const int pix = d * d, pw = conv_wgrad_persp(CHUNK_ROWS, d);
+    const int co = threadIdx.x & (CP - 1), ci = threadIdx.x >> __builtin_ctz(CP);
     const int64_t persp0 = (int64_t)blockIdx.x * pw;
     const int np = (int)(P - persp0 < pw ? P - persp0 : pw);
     float acc[9], bs = 0.f;
@@ -133,7 +145,7 @@ __global__ __launch_bounds__(256) void k_nn11_wgrad1(const uint16_t* __restrict_
     for (int t = 0; t < 9; ++t) acc[t] = 0.f;
     for (int p = 0; p < np; ++p)
         for (int o = 0; o < pix; ++o) {
-            const float gv = nn11_f32(g[((persp0 + p) * pix + o) * NN11_MAX_CP + co]);
+            const float gv = nn11_f32(g[((persp0 + p) * pix + o) * CP + co]);
             bs += gv;
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
@@ -142,22 +154,28 @@ __global__ __launch_bounds__(256) void k_nn11_wgrad1(const uint16_t* __restrict_
             }
         }
 #pragma unroll
-    for (int t = 0; t < 9; ++t) wpart[((int64_t)blockIdx.x * NN11_MAX_CP + co) * 18 + nn11_k1(ci, t)] = acc[t];
-    if (ci == 0) bpart[(int64_t)blockIdx.x * NN11_MAX_CP + co] = bs;
+    for (int t = 0; t < 9; ++t) wpart[((int64_t)blockIdx.x * CP + co) * 18 + nn11_k1(ci, t)] = acc[t];
+    if (ci == 0) bpart[(int64_t)blockIdx.x * CP + co] = bs;
 }
 
-// wgrad of layer l = 2..11.  g: G_l [P][npo][32 mt]; a: A_{l-1} [P][d^2][32 NT]; mode: the layer's forward mode (where a
-// tap's source pixel lies).  Grid (chunks, 9 taps), 256 threads: wavefront w < mt owns output channels 32 w .. 32 w + 31
-// and all NT tiles of input channels.  wpart [chunk][tap][32 mt][32 NT], bpart [chunk][128] (written by tap 0's workgroup).
-template <int NT>
-__global__ __launch_bounds__(256) void k_nn11_wgrad(const uint16_t* __restrict__ g, const uint16_t* __restrict__ a, float* __restrict__ wpart,
-                                                    float* __restrict__ bpart, int64_t P, int d, int mode, int mt) {
-    constexpr int PT = NN11_WG_PITCH, KR = NN11_WG_ROWS;
-    __shared__ __attribute__((aligned(16))) unsigned char gt[NN11_MAX_CP * PT];
+// wgrad of a layer l >= 2.  g: G_l [P][npo][32 mt]; a: A_{l-1} [P][d^2][32 NT]; mode: the layer's forward mode (where a
+// tap's source pixel lies); mt <= WAVES tiles of output channels.  Grid (chunks, 9 taps), 64 WAVES threads: wavefront
+// w < mt owns output channels 32 w .. 32 w + 31 and all NT tiles of input channels (NT x 16 accumulator registers).  A chunk
+// is conv_wgrad_persp(CHUNK_ROWS, d) records.  wpart [chunk][tap][32 mt][32 NT], bpart [chunk][32 WAVES] (written by tap 0's
+// workgroup; 0 beyond 32 mt).
+// The library holds NN_11's <3 | 4, 4, 1024> and the wide nets' <7 | 8, 8, 2048>: one workgroup over all output channels
+// of the widest layer, so that A_{l-1} is staged once.  Four waves over halves of the wide nets' output channels compile
+// to fewer registers and less LDS and stage A_{l-1} twice (profiles/nnw_grad_resource_usage.txt).
+template <int NT, int WAVES, int CHUNK_ROWS>
+__global__ __launch_bounds__(WAVES * 64) void k_conv_wgrad(const uint16_t* __restrict__ g, const uint16_t* __restrict__ a, float* __restrict__ wpart,
+                                                           float* __restrict__ bpart, int64_t P, int d, int mode, int mt) {
+    constexpr int PT = NN11_WG_PITCH, KR = NN11_WG_ROWS, THREADS = WAVES * 64, MAX_CP = WAVES * 32;
+    static_assert(NT <= WAVES, "the input channels lie inside the widest image");
+    __shared__ __attribute__((aligned(16))) unsigned char gt[MAX_CP * PT];
     __shared__ __attribute__((aligned(16))) unsigned char at[NT * 32 * PT];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int tap = (int)blockIdx.y, pix = d * d, od = mode == NN11_VALID ? d - 2 : d, npo = od * od;
-    const int cpo = 32 * mt, cpi = 32 * NT, pw = nn11_wgrad_persp(d);
+    const int cpo = 32 * mt, cpi = 32 * NT, pw = conv_wgrad_persp(CHUNK_ROWS, d);
     const int64_t persp0 = (int64_t)blockIdx.x * pw;
     const int np = (int)(P - persp0 < pw ? P - persp0 : pw);
     const int rows = np * npo;
@@ -174,7 +192,7 @@ __global__ __launch_bounds__(256) void k_nn11_wgrad(const uint16_t* __restrict__
     for (int r0 = 0; r0 < rows; r0 += KR) {
         __syncthreads();                                                    // the previous stage has been read
         // stage, transposed: an item is two neighbouring rows x 8 channels, stored as 8 words (row pair of one channel)
-        for (int it = tid; it < 32 * (cpo / 8); it += 256) {
+        for (int it = tid; it < 32 * (cpo / 8); it += THREADS) {
             const int rp = it & 31, ch = it >> 5, row = r0 + 2 * rp;
             uint4 v0 = make_uint4(0, 0, 0, 0), v1 = v0;
             if (row < rows) v0 = *reinterpret_cast<const uint4*>(g0 + (int64_t)row * cpo + ch * 8);
@@ -186,7 +204,7 @@ __global__ __launch_bounds__(256) void k_nn11_wgrad(const uint16_t* __restrict__
                 *reinterpret_cast<uint32_t*>(gt + (ch * 8 + j) * PT + rp * 4) = lo | (hi << 16);
             }
         }
-        for (int it = tid; it < 32 * (cpi / 8); it += 256) {
+        for (int it = tid; it < 32 * (cpi / 8); it += THREADS) {
             const int rp = it & 31, ch = it >> 5;
             uint4 v[2];
 #pragma unroll
@@ -235,7 +253,7 @@ __global__ __launch_bounds__(256) void k_nn11_wgrad(const uint16_t* __restrict__
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[(int64_t)(8 * q + 4 * h + e) * cpi + 32 * n + r] = acc[n][4 * q + e];
     }
-    if (tap == 0 && tid < NN11_MAX_CP) bpart[(int64_t)blockIdx.x * NN11_MAX_CP + tid] = tid < cpo ? bs : 0.f;
+    if (tap == 0 && tid < MAX_CP) bpart[(int64_t)blockIdx.x * MAX_CP + tid] = tid < cpo ? bs : 0.f;
 }
 
 // dW (torch layout [cout][cin][taps], written) = the partial images summed in chunk order; db likewise.  wpart is

@@ -9,13 +9,11 @@ include/toricenv.h).  policy.py re-exports the four classes.
   NN11Grad       src/Learner_mp.py:140-160 (forward, loss head and backward pass as HIP kernels)
   NN11Optimizer  src/Learner_mp.py:81-84 (Adam / RMSprop on the masters and the re-pack, one HIP launch)
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._forward import ForwardHandle, PlainConvNet, _check_stack, _pointers
-from ._lib import Handle, _ptr, check, require_gpu, to_device
+from ._forward import ForwardHandle, GradHandle, PlainConvNet, _check_stack, _pointers
+from ._lib import _ptr, to_device
 
 CHANNELS = (2, 128, 128, 120, 111, 104, 103, 90, 80, 73, 71, 64)
 NAMES = [f"conv{i + 1}" for i in range(11)] + ["linear1"]       # the layers, in the order of every list of 12 below
@@ -89,58 +87,27 @@ class NN11Forward(ForwardHandle):
         self._call(self._L.tq_nn11_check)
 
 
-class NN11Grad(Handle):
+class NN11Grad(GradHandle):
     """NN_11's learner step as HIP kernels (tq_nn11_grad_*; numerics contract in include/toricenv.h): the forward with
     every layer kept, the gather of Q(s,a), the weighted squared error and the backward pass, bf16 operands with f32
     accumulation.  ``model``: a torch NN_11 on ``device`` whose f32 parameters are the masters -- ``backward`` fills their
     ``.grad`` (written, not accumulated), the caller's optimizer steps them, ``load()`` re-reads them.  One handle, one
     stream; ``max_batch`` (1..4096) sizes the scratch."""
 
-    _destroy = "tq_nn11_grad_destroy"
+    _create, _load, _step = "tq_nn11_grad_create", "tq_nn11_grad_load", "tq_nn11_grad_step"
+    _check, _destroy = "tq_nn11_grad_check", "tq_nn11_grad_destroy"
 
     def __init__(self, model, system_size, device, max_batch=256):
-        self.device = require_gpu(device)
-        self.system_size = int(system_size)
-        self.max_batch = int(max_batch)
-        self.model = model
-        self._params = [(getattr(model, n).weight, getattr(model, n).bias) for n in NAMES]
-        _check_params(self._params, self.system_size, self.device)
-        self._L = _lib.load()
-        self._h = C.c_void_p(None)
-        check(self._L.tq_nn11_grad_create(C.byref(self._h), self.system_size, self.max_batch, self.device.index))
-        self.load()
+        super().__init__(model, system_size, device, max_batch)
+
+    def _masters(self, model):
+        pairs = [(getattr(model, n).weight, getattr(model, n).bias) for n in NAMES]
+        _check_params(pairs, self.system_size, self.device)
+        return pairs
 
     def load(self):
         """Re-reads the model's parameters (packed on the device, no allocation): after every optimizer step."""
-        self._call(self._L.tq_nn11_grad_load, _pointers([w for w, _ in self._params]), _pointers([b for _, b in self._params]))
-        return self
-
-    def backward(self, state, actions_idx, y, weights=None):
-        """Learner_mp.py:140-160 for one batch: ``state`` (n, 2, d, d) float32 / float16 / bfloat16 / uint8,
-        ``actions_idx`` int64 (n,) in 0..2, ``y`` the targets, ``weights`` the importance weights (None: ones) ->
-        (loss f32 (n,) = weights * (y - Q(s,a))^2, q f32 (n, 3)); every parameter's ``.grad`` holds the gradient of
-        loss.mean().  An action outside 0..2 gets loss 0 and no gradient, and check() raises for it."""
-        dev = self.device
-        state, dtype = _check_stack(state, self.system_size, dev, "state")
-        n = state.shape[0]
-        a = to_device(actions_idx, torch.int64, dev).reshape(-1)
-        y = to_device(y.detach() if torch.is_tensor(y) else y, torch.float32, dev).reshape(-1)
-        w = None if weights is None else to_device(weights, torch.float32, dev).reshape(-1)
-        if a.numel() != n or y.numel() != n or (w is not None and w.numel() != n):
-            raise ValueError("actions_idx / y / weights must have one entry per record")
-        for wt, bt in self._params:
-            for p in (wt, bt):
-                if p.grad is None or not p.grad.is_contiguous():
-                    p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
-        q = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
-        self._call(self._L.tq_nn11_grad_step, _ptr(state), dtype, n, _ptr(a), _ptr(y), _ptr(w), _ptr(q), _ptr(loss),
-                   _pointers([wt.grad for wt, _ in self._params]), _pointers([bt.grad for _, bt in self._params]))
-        return loss, q
-
-    def check(self):
-        """Reads and clears the device error latch (synchronises): ValueError for an action outside 0..2."""
-        self._call(self._L.tq_nn11_grad_check)
+        return super().load()
 
 
 class NN11Optimizer:

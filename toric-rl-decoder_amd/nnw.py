@@ -11,13 +11,11 @@ classes.
   NNWideForward  either one's forward as bf16 MFMA kernels
   NNWideGrad     src/Learner_mp.py:140-160 for either one (forward, loss head and backward pass as HIP kernels)
 """
-import ctypes as C
-
 import torch
 
 from . import _lib
-from ._forward import ForwardHandle, PlainConvNet, _check_stack, _pointers, match_net
-from ._lib import Handle, _ptr, check, require_gpu, to_device
+from ._forward import ForwardHandle, GradHandle, PlainConvNet, _pointers, match_net
+from ._lib import to_device
 
 CHANNELS = {
     _lib.TQ_NET_NN8: (2, 256, 256, 240, 224, 220, 215, 205, 200),
@@ -84,7 +82,7 @@ class NNWideForward(ForwardHandle):
         return self                                                  # where any copies made above are freed in stream order
 
 
-class NNWideGrad(Handle):
+class NNWideGrad(GradHandle):
     """NN_8's or NN_17's learner step as HIP kernels (tq_nnw_grad_*; numerics contract in include/toricenv.h): the
     forward with every layer kept, the gather of Q(s,a), the weighted squared error and the backward pass, bf16 operands
     with f32 accumulation -- NN11Grad's interface, and ``policy.learnerStep`` takes either.  ``model``: a torch NN_8 /
@@ -93,19 +91,15 @@ class NNWideGrad(Handle):
     nets have no optimizer kernel) steps them, ``load()`` re-reads them.  One handle, one stream; ``max_batch`` (1..4096)
     sizes the scratch: every layer's activation image is kept."""
 
-    _destroy = "tq_nnw_grad_destroy"
+    _create, _load, _step = "tq_nnw_grad_create", "tq_nnw_grad_load", "tq_nnw_grad_step"
+    _check, _destroy = "tq_nnw_grad_check", "tq_nnw_grad_destroy"
 
     def __init__(self, model, system_size, device, max_batch=256):
-        self.device = require_gpu(device)
-        self.system_size = int(system_size)
-        self.max_batch = int(max_batch)
-        self.model = model
-        self.net = which_net(model.state_dict(), self.system_size)      # a wrong net is refused before the device is asked for
-        self._params = self._masters(model)
-        self._L = _lib.load()
-        self._h = C.c_void_p(None)
-        check(self._L.tq_nnw_grad_create(C.byref(self._h), self.net, self.system_size, self.max_batch, self.device.index))
-        self.load()
+        super().__init__(model, system_size, device, max_batch)
+
+    def _net(self, model):
+        self.net = which_net(model.state_dict(), self.system_size)
+        return (self.net,)
 
     def _masters(self, model):
         """(weight, bias) per layer of names(net); ValueError unless ``model`` is this handle's net with contiguous float32
@@ -119,38 +113,3 @@ class NNWideGrad(Handle):
                 if p.dtype != torch.float32 or p.device != self.device or not p.is_contiguous():
                     raise ValueError(f"{n}: expected a contiguous float32 parameter on {self.device}, got {p.dtype} on {p.device}")
         return pairs
-
-    def load(self, model=None):
-        """Re-reads the model's parameters (packed on the device, no allocation): after every optimizer step.  ``model``:
-        another model of the same net to take as the masters from now on."""
-        if model is not None:
-            self._params, self.model = self._masters(model), model
-        self._call(self._L.tq_nnw_grad_load, _pointers([w for w, _ in self._params]), _pointers([b for _, b in self._params]))
-        return self
-
-    def backward(self, state, actions_idx, y, weights=None):
-        """Learner_mp.py:140-160 for one batch: ``state`` (n, 2, d, d) float32 / float16 / bfloat16 / uint8,
-        ``actions_idx`` int64 (n,) in 0..2, ``y`` the targets, ``weights`` the importance weights (None: ones) ->
-        (loss f32 (n,) = weights * (y - Q(s,a))^2, q f32 (n, 3)); every parameter's ``.grad`` holds the gradient of
-        loss.mean().  An action outside 0..2 gets loss 0 and no gradient, and check() raises for it."""
-        dev = self.device
-        state, dtype = _check_stack(state, self.system_size, dev, "state")
-        n = state.shape[0]
-        a = to_device(actions_idx, torch.int64, dev).reshape(-1)
-        y = to_device(y.detach() if torch.is_tensor(y) else y, torch.float32, dev).reshape(-1)
-        w = None if weights is None else to_device(weights, torch.float32, dev).reshape(-1)
-        if a.numel() != n or y.numel() != n or (w is not None and w.numel() != n):
-            raise ValueError("actions_idx / y / weights must have one entry per record")
-        for wt, bt in self._params:
-            for p in (wt, bt):
-                if p.grad is None or not p.grad.is_contiguous():
-                    p.grad = torch.empty_like(p, memory_format=torch.contiguous_format)
-        q = torch.empty((n, 3), dtype=torch.float32, device=dev)
-        loss = torch.empty(n, dtype=torch.float32, device=dev)
-        self._call(self._L.tq_nnw_grad_step, _ptr(state), dtype, n, _ptr(a), _ptr(y), _ptr(w), _ptr(q), _ptr(loss),
-                   _pointers([wt.grad for wt, _ in self._params]), _pointers([bt.grad for _, bt in self._params]))
-        return loss, q
-
-    def check(self):
-        """Reads and clears the device error latch (synchronises): ValueError for an action outside 0..2."""
-        self._call(self._L.tq_nnw_grad_check)
